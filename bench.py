@@ -8,11 +8,16 @@ configs are parity-test cases; ``--workload c3|n2tet|rt2tet|dg6tet|hex ...`` tim
 
 One "step" = one pass of the hot path over the whole batch, inputs and outputs resident in HBM.
 
+A plain run does only what the headline figure needs: set up, ramp the clock, W warm-up steps, K timed steps, the outputs
+of the last step written out with ``--dump-outputs DIR``, one line.  ``--full`` adds everything else the line can carry:
+the same W + K steps from an idle GPU (``ms_per_step_cold``), per-kernel timing and the roofline, the fill probe, the
+check against the CPU oracle (``--check``, the whole batch by default), the CPU baseline and, with N > 1, the all-gather leg.
+
 Multi-GPU (one process per GPU): either launched by ``python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N`` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or bare ``python bench.py --gpus N``,
 which starts the N ranks itself BEFORE anything touches the GPU.  Every rank tabulates its own block of requests
 (weak scaling, no data-path collective: requests are independent); ``value`` is that compute-only aggregate.  With
-N > 1 the line also carries ``allgather``: the same step followed by / overlapped with the RCCL exchange that
+N > 1 and ``--full`` the line also carries ``allgather``: the same step followed by / overlapped with the RCCL exchange that
 replicates all tables on every GPU (fiat_amd/distributed.py -> fx_allgather_tables), timed separately.
 
 Prints ONE JSON line on rank 0.
@@ -40,6 +45,7 @@ F64_PEAK_TFLOPS = 32 * 1024 * 2.4e9 / 1e12
 PEER_GRACE_S = 15.0     # ranks != 0 keep waiting this much longer than rank 0's all-gather watchdog (run(): rank 0 prints)
 TERM_GRACE_S = 5.0      # spawn_ranks: after the first failed rank the others get this long to leave on their own
 CLOCK_RAMP_MS = 60.0    # untimed launches before the W warm-up steps: the shader clock needs tens of ms after idle
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: array bytes in all, below 64 MB with the .npy headers
 
 WORKLOADS = {
     # name: (family, sd, degree, order, npts, default batch per GPU)
@@ -64,6 +70,30 @@ def synth_points(sd, nreq, npts, seed):
     rng = np.random.default_rng(seed)
     e = rng.exponential(size=(nreq, npts, sd + 1))
     return (e / e.sum(axis=-1, keepdims=True))[..., 1:].copy()
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write ``{name: tensor}`` (the tables a caller of the timed path receives) as ``out_dir/<name>.npy``.  An output
+    larger than its share of ``budget`` is cut to a fixed, seeded sample of its requests (rows of dim 0, kept in order),
+    the same for every run of the same arguments, so that two builds can be compared output for output.
+    Returns {name: requests written}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // len(outputs)
+    written = {}
+    for name, t in outputs.items():
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name}: {t.dtype} output, --dump-outputs writes float32 / float64 only")
+        n = t.shape[0]
+        keep = min(n, share // (t[0].numel() * t.element_size()))
+        if keep < 1:
+            raise ValueError(f"{name}: one request of {tuple(t.shape[1:])} exceeds the {share} B share of the dump")
+        if keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        written[name] = keep
+    return written
 
 
 def host_cpu_share():
@@ -152,6 +182,9 @@ class SimplexWorkload:
                 p["ps"].tabulate_batch_shared(self.order, p["ref_pts"], p["verts"], mapping=p["el"].mapping()[0], out=p["out"])
             else:
                 p["ps"].tabulate_batch(self.order, p["pts"], out=p["out"])
+
+    def outputs(self):
+        return {p["family"]: p["out"] for p in self.parts}
 
     def produce_rows(self, lo, hi, rows):
         """Tabulate requests [lo, hi) of the (single-part) batch into ``rows`` (a view of a gather buffer)."""
@@ -251,6 +284,9 @@ class HexWorkload:
 
     def step(self):
         self.el.tabulate_batch(1, self.grid, out=self.out, grid=True)
+
+    def outputs(self):
+        return {"TensorProductElement": self.out}
 
     def produce_rows(self, lo, hi, rows):
         self.el.tabulate_batch(1, self.grid[lo:hi], out=rows.view(hi - lo, 4, 125, 125), grid=True)
@@ -402,17 +438,18 @@ def run(args):
     batch = wl.batch
     stream = torch.cuda.current_stream()
 
-    # the driver's protocol WITHOUT the ramp, for the record: W warm-up + K timed launches from an idle GPU
-    torch.cuda.synchronize()
-    time.sleep(0.5)
-    for _ in range(args.warmup):
-        wl.step()
-    torch.cuda.synchronize()
-    t_cold = time.perf_counter()
-    for _ in range(args.steps):
-        wl.step()
-    torch.cuda.synchronize()
-    ms_per_step_cold = (time.perf_counter() - t_cold) / args.steps * 1e3
+    if args.full:
+        # the driver's protocol WITHOUT the ramp, for the record: W warm-up + K timed launches from an idle GPU
+        torch.cuda.synchronize()
+        time.sleep(0.5)
+        for _ in range(args.warmup):
+            wl.step()
+        torch.cuda.synchronize()
+        t_cold = time.perf_counter()
+        for _ in range(args.steps):
+            wl.step()
+        torch.cuda.synchronize()
+        ms_per_step_cold = (time.perf_counter() - t_cold) / args.steps * 1e3
 
     # clock ramp (disclosed in the line, not part of W): the first launches after idle run ~25 % slower
     t_ramp = time.perf_counter()
@@ -438,7 +475,70 @@ def run(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what the last timed step computed, before anything else launches (rank 0's block)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(), args.dump_outputs)
+    if args.full:
+        roofline = measure_roofline(wl, args, rank, batch, stream, ms_per_step_cold)
 
+    # parity of the timed output against the CPU oracle (never inside the timed region)
+    check = args.check if args.check is not None else (-1 if args.full else 0)
+    max_err = None
+    if check and rank == 0:
+        max_err = wl.max_rel_err(check)
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "element tabulations/sec (basis+grad, fp64) for batched P3 tet"
+                      if args.workload == "p3tet" else f"element tabulations/sec ({args.workload})",
+            "value": batch * world * args.steps / elapsed,
+            "unit": "tabulations/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": wl.describe(), "requests_per_gpu": batch, "points_per_request": wl.npts, "order": wl.order,
+                       "points": "one 23-point rule on the reference cell, per-request physical cells" if args.shared_points
+                                 else "random per request",
+                       "sharding": "independent requests, contiguous blocks per rank, no data-path collective",
+                       "world_size": world, "launch": "self-spawned ranks" if os.environ.get("FIAT_AMD_BENCH_SPAWNED") else
+                                     ("torch.distributed.run" if world > 1 else "single process"),
+                       "clock_ramp_ms_before_warmup": CLOCK_RAMP_MS, "clock_ramp_steps": ramp_steps,
+                       **({"policy": args.policy} if args.policy else {})},
+            "max_rel_err_vs_oracle": max_err,
+            "requests_checked_vs_oracle": getattr(wl, "checked", None),
+        }
+        if args.full:
+            # same W + K launches from an idle GPU, before the clock ramp (this rank)
+            line.update(ms_per_step_cold=ms_per_step_cold, roofline=roofline)
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = wl.cpu_baseline()
+
+    if (args.full or args.allgather) and world > 1 and not args.no_allgather and len(wl.parts) == 1 and not args.shared_points:
+        failed = guarded_leg(line, rank, args.allgather_timeout, barrier,
+                             lambda: allgather_leg(wl, world, rank, args, barrier))
+    else:
+        failed = False
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+    if failed:
+        print("bench.py: the all-gather leg failed (see the line's \"allgather\" field)", file=sys.stderr, flush=True)
+        sys.stdout.flush()
+        os._exit(3)     # peers may be stuck in a collective: no orderly teardown of the process group
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def measure_roofline(wl, args, rank, batch, stream, ms_per_step_cold):
+    """--full: per-kernel launch times in runs of their own, algorithmic HBM / fp64 rates against the peaks, the fill probe,
+    and the PMC traffic of an earlier profile of the same command when profiles/ holds one."""
+    import torch
     # dominant kernel(s): average launch duration from HIP events on the launch stream
     kt = wl.kernel_times(max(5, args.steps), stream)
     kernel_ms = sum(k[1] for k in kt)
@@ -494,57 +594,7 @@ def run(args):
                                               "of this command on an earlier box, NOT measured in this run")
         except Exception:
             pass
-
-    # parity of the timed output against the CPU oracle (never inside the timed region)
-    max_err = None
-    if args.check and rank == 0:
-        max_err = wl.max_rel_err(args.check)
-
-    line = None
-    if rank == 0:
-        line = {
-            "metric": "element tabulations/sec (basis+grad, fp64) for batched P3 tet"
-                      if args.workload == "p3tet" else f"element tabulations/sec ({args.workload})",
-            "value": batch * world * args.steps / elapsed,
-            "unit": "tabulations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_cold": ms_per_step_cold,      # same W + K launches from an idle GPU, before the clock ramp (this rank)
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": wl.describe(), "requests_per_gpu": batch, "points_per_request": wl.npts, "order": wl.order,
-                       "points": "one 23-point rule on the reference cell, per-request physical cells" if args.shared_points
-                                 else "random per request",
-                       "sharding": "independent requests, contiguous blocks per rank, no data-path collective",
-                       "world_size": world, "launch": "self-spawned ranks" if os.environ.get("FIAT_AMD_BENCH_SPAWNED") else
-                                     ("torch.distributed.run" if world > 1 else "single process"),
-                       "clock_ramp_ms_before_warmup": CLOCK_RAMP_MS, "clock_ramp_steps": ramp_steps,
-                       **({"policy": args.policy} if args.policy else {})},
-            "roofline": roofline,
-            "max_rel_err_vs_oracle": max_err,
-            "requests_checked_vs_oracle": getattr(wl, "checked", None),
-        }
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = wl.cpu_baseline()
-
-    if world > 1 and not args.no_allgather and len(wl.parts) == 1 and not args.shared_points:
-        failed = guarded_leg(line, rank, args.allgather_timeout, barrier,
-                             lambda: allgather_leg(wl, world, rank, args, barrier))
-    else:
-        failed = False
-        if rank == 0:
-            print(json.dumps(line), flush=True)
-    if failed:
-        print("bench.py: the all-gather leg failed (see the line's \"allgather\" field)", file=sys.stderr, flush=True)
-        sys.stdout.flush()
-        os._exit(3)     # peers may be stuck in a collective: no orderly teardown of the process group
-    if world > 1:
-        dist.destroy_process_group()
+    return roofline
 
 
 def guarded_leg(line, rank, timeout, barrier, leg):
@@ -792,7 +842,7 @@ def main():
     ap.add_argument("--workload", default="p3tet", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="requests per GPU (default: the workload's)")
     ap.add_argument("--no-allgather", action="store_true", help="N > 1: skip the with-gather leg")
-    ap.add_argument("--allgather", action="store_true", help="(kept for compatibility: the leg runs by default when N > 1)")
+    ap.add_argument("--allgather", action="store_true", help="N > 1: run the with-gather leg without --full")
     ap.add_argument("--allgather-impl", default="auto", choices=["auto", "rccl", "torch"],
                     help="rccl = fx_allgather_tables through the C ABI, torch = torch.distributed collectives")
     ap.add_argument("--allgather-algo", default="direct", choices=["direct", "ring"])
@@ -810,8 +860,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--policy", default="", help="measurement only: kernel-selection policy names (fx_ctx_set_policy), comma separated; "
                                                  "disclosed in config.policy -- the default line is the one without it")
-    ap.add_argument("--check", type=int, default=-1,
-                    help="requests verified against the CPU oracle after timing (-1: the whole batch, 0: none)")
+    ap.add_argument("--check", type=int, default=None,
+                    help="requests verified against the CPU oracle after timing (-1: the whole batch, 0: none; "
+                         "default -1 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: cold timing, per-kernel roofline, fill probe, oracle check, "
+                         "CPU baseline, N > 1 all-gather leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the tables of the last timed step (rank 0) as DIR/<family>.npy, fp64; larger than "
+                         f"{DUMP_BUDGET_BYTES // 1_000_000} MB in all: a fixed seeded sample of the requests")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")

@@ -120,8 +120,8 @@ def test_guarded_leg_orderly_failure():
 def test_stuck_allgather_leg_is_a_failure_not_a_success(stuck):
     """A rank that never joins the exchange: rank 0's watchdog (always the first to fire) still prints the compute-only line,
     with the error inside, and the job exits NON-ZERO -- a hung collective must not look like success to the driver."""
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2000", "--check", "50",
-                          "--no-cpu-baseline", "--allgather-timeout", "20"], capture_output=True, text=True,
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--batch", "2000",
+                          "--check", "50", "--no-cpu-baseline", "--allgather-timeout", "20"], capture_output=True, text=True,
                          env=_env(FIAT_AMD_BENCH_BACKEND="gloo", FIAT_AMD_BENCH_FORCE_GATHER_TIMEOUT=str(stuck)), timeout=900)
     assert res.returncode != 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -137,7 +137,7 @@ def test_torchrun_launch_with_a_failing_peer_keeps_the_line(hook):
     """The driver's launch line with rank 1 hanging / dying inside the exchange: torch.distributed.run SIGTERMs the siblings
     of the first failed rank -- the compute-only line must be on stdout regardless."""
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                          "127.0.0.1", "--master-port", str(_port()), BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "127.0.0.1", "--master-port", str(_port()), BENCH, "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
                           "--batch", "2000", "--check", "50", "--allgather-timeout", "20"], capture_output=True, text=True,
                          env=_env(FIAT_AMD_BENCH_BACKEND="gloo", **{hook: "1"}), timeout=900)
     assert res.returncode != 0, res.stderr[-2000:]
@@ -152,8 +152,8 @@ def test_torchrun_launch_with_a_failing_peer_keeps_the_line(hook):
 @pytest.mark.gpu
 def test_allgather_verify_two_ranks():
     """--allgather-verify: both ranks tabulate the same requests and compare every gathered block with their own."""
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3000", "--check", "50",
-                          "--no-cpu-baseline", "--allgather-verify"], capture_output=True, text=True,
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--batch", "3000",
+                          "--check", "50", "--no-cpu-baseline", "--allgather-verify"], capture_output=True, text=True,
                          env=_env(FIAT_AMD_BENCH_BACKEND="gloo"), timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -167,7 +167,7 @@ def test_allgather_verify_two_ranks():
 def test_bare_two_rank_launch_on_one_gpu():
     """FIAT_AMD_BENCH_BACKEND=gloo lets two ranks share the one GPU of this box: the parent spawns them, both tabulate their
     own block, the with-gather leg runs through fiat_amd/distributed.py, rank 0 prints ONE line with n_gpus = 2."""
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4000",
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--batch", "4000",
                           "--allgather-chunks", "4"], capture_output=True, text=True,
                          env=_env(FIAT_AMD_BENCH_BACKEND="gloo"), timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -186,8 +186,8 @@ def test_bare_two_rank_launch_on_one_gpu():
 @pytest.mark.gpu
 def test_two_ranks_with_the_staging_ring():
     """Outputs too large to replicate travel through the ring of staging buffers (forced here on a small batch)."""
-    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3000", "--check", "100",
-                          "--allgather-mode", "ring", "--allgather-chunks", "4"], capture_output=True, text=True,
+    res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--batch", "3000",
+                          "--check", "100", "--allgather-mode", "ring", "--allgather-chunks", "4"], capture_output=True, text=True,
                          env=_env(FIAT_AMD_BENCH_BACKEND="gloo"), timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -206,8 +206,9 @@ def test_driver_style_torchrun_launch_two_ranks():
     port = s.getsockname()[1]
     s.close()
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "3000",
-                          "--check", "200"], capture_output=True, text=True, env=_env(FIAT_AMD_BENCH_BACKEND="gloo"), timeout=900)
+                          "--master-port", str(port), BENCH, "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
+                          "--batch", "3000", "--check", "200"],
+                         capture_output=True, text=True, env=_env(FIAT_AMD_BENCH_BACKEND="gloo"), timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]

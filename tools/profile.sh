@@ -7,7 +7,8 @@ shift || true
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --check 0 $*"   # the driver's step counts
+# the driver's step counts; --full adds the launches summarize_profile.py splits into phases (cold pass, HIP-event timing)
+CMD="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --check 0 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_ANY \
    --output-format csv -d $OUT/pmc_sq1 -- $CMD > $OUT/pmc_sq1.log 2>&1 || true
