@@ -35,6 +35,7 @@ from .regge import Regge  # noqa: F401
 from .hellan_herrmann_johnson import HellanHerrmannJohnson  # noqa: F401
 from .gopalakrishnan_lederer_schoberl import GopalakrishnanLedererSchoberlSecondKind  # noqa: F401
 from .tensor_product import FlattenedDimensions, TensorProductElement  # noqa: F401
+from .bernstein import Bernstein  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
@@ -54,6 +55,7 @@ supported_elements = {
     "Gopalakrishnan-Lederer-Schoberl 2nd kind": GopalakrishnanLedererSchoberlSecondKind,
     "TensorProductElement": TensorProductElement,
     "FlattenedDimensions": FlattenedDimensions,
+    "Bernstein": Bernstein,
 }
 
 # (FIAT/__init__.py:130-131)

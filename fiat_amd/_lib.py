@@ -102,6 +102,10 @@ _SIGS = {
     "fx_ctx_check": (c_int, [c_void_p, c_void_p]),
     "fx_time_tabulate_batch": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int, POINTER(c_float)]),
+    "fx_bernstein_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "fx_bernstein_tabulate_shared": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)

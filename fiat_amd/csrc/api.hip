@@ -163,6 +163,19 @@ struct fx_ctx {
 };
 constexpr int FX_QUEUE_SLOTS = 64;  // counters handed to consecutive launches round-robin (128 B apart)
 
+// for the entry points of the other translation units (bernstein.hip): fx_last_error's message, the context's device facts
+namespace fx {
+int set_error(int code, const char* msg) {
+    g_err = msg;
+    return code;
+}
+void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu) {
+    *device = ctx->device;
+    *num_cu = ctx->num_cu;
+    *lds_per_cu = ctx->lds_per_cu;
+}
+}  // namespace fx
+
 #include "comm.hpp"
 
 constexpr int FX_MAX_ORDER = 8;  // highest derivative order served (orders > 2 through differentiation matrices)

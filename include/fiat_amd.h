@@ -369,6 +369,20 @@ int fx_time_tabulate_batch(fx_ctx* ctx, const fx_element* elem, int order,
                            const double* verts, double* out, void* stream,
                            int reps, float* ms);
 
+/* ---- Bernstein elements (FIAT/bernstein.py) --------------------------------------
+ * Bernstein.tabulate: the Bernstein-Bezier basis evaluated directly in barycentric coordinates, no expansion set.
+ * cell host [(sd+1)][sd] = vertices of the element's own simplex (any non-degenerate simplex);
+ * pts device [nreq][npts][sd]; verts device [nreq][sd+1][sd] or NULL; out device [nreq][ntab][ndof][npts],
+ * ndof = C(n+sd, sd) in mis(sd+1, n) order, ntab = fx_num_tables(sd, order).  With verts the tables are the basis
+ * functions of Bernstein(verts[r], n) at physical points, derivatives with respect to the physical coordinates.
+ * 0 <= n <= 16; order <= 8 on the element's cell, <= 4 with verts (FX_ENOTIMPL beyond).  Where the derivative order
+ * equals the degree (>= 2) the value is the exact n!-scaled one (the reference returns 1 there: INTEGRATION.md 6). */
+int fx_bernstein_tabulate_batch(fx_ctx* ctx, int sd, int n, const double* cell, int order, int64_t nreq, int npts,
+                                const double* pts, const double* verts, double* out, void* stream);
+/* one reference point set ref_pts device [npts][sd] on `cell`, pushed to every verts[r] (affine; verts required) */
+int fx_bernstein_tabulate_shared(fx_ctx* ctx, int sd, int n, const double* cell, int order, int64_t nreq, int npts,
+                                 const double* ref_pts, const double* verts, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
