@@ -36,6 +36,8 @@ from .hellan_herrmann_johnson import HellanHerrmannJohnson  # noqa: F401
 from .gopalakrishnan_lederer_schoberl import GopalakrishnanLedererSchoberlSecondKind  # noqa: F401
 from .tensor_product import FlattenedDimensions, TensorProductElement  # noqa: F401
 from .bernstein import Bernstein  # noqa: F401
+from .enriched import EnrichedElement  # noqa: F401
+from .hdivcurl import Hcurl, Hdiv  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset

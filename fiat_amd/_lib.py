@@ -106,6 +106,12 @@ _SIGS = {
                                             c_void_p, c_void_p]),
     "fx_bernstein_tabulate_shared": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "fx_hdivcurl_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                           c_int, c_void_p, c_void_p, c_void_p]),
+    "fx_hdivcurl_tabulate_grid_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "fx_table_place_batch": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -174,6 +174,7 @@ void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu) {
     *num_cu = ctx->num_cu;
     *lds_per_cu = ctx->lds_per_cu;
 }
+void line_facts(const fx_line_element* e, fxk::LineDesc* L);  // (below, after fx_line_element)
 }  // namespace fx
 
 #include "comm.hpp"
@@ -2709,6 +2710,11 @@ static fxk::LineDesc line_desc(const fx_line_element* e) {
     L.nn = e->nn;
     return L;
 }
+
+}  // extern "C"
+// the node data of a 1-D Lagrange element, for the other translation units (hdivcurl.hip)
+void fx::line_facts(const fx_line_element* e, fxk::LineDesc* L) { *L = line_desc(e); }
+extern "C" {
 
 int fx_line_tabulate_batch(fx_ctx* ctx, const fx_line_element* e, int order, int64_t nreq, int npts, const double* pts,
                            double* out, void* stream) {

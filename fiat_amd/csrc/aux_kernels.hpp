@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "line_basis.hpp"
 #include "store.hpp"
 
 namespace fxk {
@@ -140,91 +141,6 @@ __global__ __launch_bounds__(256) void vandermonde_solve_kernel(int n, int m, co
     __syncthreads();
     for (int e = tid; e < n * m; e += nt) Xall[sys * (size_t)n * m + e] = R[e];
     if (tid == 0) info_all[sys] = s_info;
-}
-
-// ---------------------------------------------------------------------------
-// 1-D Lagrange basis by the second barycentric formula
-// (barycentric_interpolation.py:22-47).  tab layout [k][i] in registers of the
-// calling lane for one point; NN_MAX bounds the node count.
-constexpr int NN_MAX = 16;
-
-struct LineDesc {
-    const double* nodes;  // [nn]
-    const double* wts;    // [nn] barycentric weights
-    const double* dmat;   // [nn][nn] differentiation matrix
-    int nn;
-};
-
-// values phi[i] at x; exact Kronecker delta when x hits a node
-// (barycentric_interpolation.py:35-40: NaN -> 1 after the normalisation).
-// (node data through the constant address space: never written while a kernel runs, so the loads are scalar)
-typedef const __attribute__((address_space(4))) double LineConst;
-
-__device__ __forceinline__ void lagrange_values(const LineDesc& L, double x, double* phi) {
-    LineConst* nodes = (LineConst*)(unsigned long long)L.nodes;
-    LineConst* wts = (LineConst*)(unsigned long long)L.wts;
-    double sum = 0.0;
-    int hit = -1;
-#pragma unroll
-    for (int i = 0; i < NN_MAX; ++i) {
-        if (i < L.nn) {
-            double d = x - nodes[i];
-            if (d == 0.0) hit = i;
-            double t = wts[i] / d;
-            phi[i] = t;
-            sum += t;
-        }
-    }
-    double inv = 1.0 / sum;
-#pragma unroll
-    for (int i = 0; i < NN_MAX; ++i) {
-        if (i < L.nn) phi[i] = (hit >= 0) ? ((i == hit) ? 1.0 : 0.0) : phi[i] * inv;
-    }
-}
-
-// out = dmat . in
-__device__ __forceinline__ void lagrange_diff(const LineDesc& L, const double* in, double* out) {
-    LineConst* dmat = (LineConst*)(unsigned long long)L.dmat;
-#pragma unroll
-    for (int i = 0; i < NN_MAX; ++i) {
-        if (i < L.nn) {
-            double s = 0.0;
-#pragma unroll
-            for (int j = 0; j < NN_MAX; ++j)
-                if (j < L.nn) s += dmat[i * L.nn + j] * in[j];
-            out[i] = s;
-        }
-    }
-}
-
-// the same with a compile-time node count: every index is a constant, the node data are uniform loads
-template <int NN> __device__ __forceinline__ void lagrange_values_n(const LineDesc& L, double x, double (&phi)[NN]) {
-    LineConst* nodes = (LineConst*)(unsigned long long)L.nodes;
-    LineConst* wts = (LineConst*)(unsigned long long)L.wts;
-    double sum = 0.0;
-    int hit = -1;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) {
-        const double d = x - nodes[i];
-        if (d == 0.0) hit = i;
-        const double t = wts[i] / d;
-        phi[i] = t;
-        sum += t;
-    }
-    const double inv = 1.0 / sum;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) phi[i] = hit >= 0 ? (i == hit ? 1.0 : 0.0) : phi[i] * inv;
-}
-
-template <int NN> __device__ __forceinline__ void lagrange_diff_n(const LineDesc& L, const double (&in)[NN], double (&out)[NN]) {
-    LineConst* dmat = (LineConst*)(unsigned long long)L.dmat;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < NN; ++j) s += dmat[i * NN + j] * in[j];
-        out[i] = s;
-    }
 }
 
 // out[r][k][i][p], one thread per (r, p)

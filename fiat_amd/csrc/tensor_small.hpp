@@ -18,33 +18,6 @@
 
 namespace fxk {
 
-// derivative multi-indices in mis() order (polynomial_set.py:23-32), at compile time
-template <int NF, int ORDER> struct TensorAlpha {
-    static constexpr int NTAB = NF == 2 ? (ORDER + 1) * (ORDER + 2) / 2 : (ORDER + 1) * (ORDER + 2) * (ORDER + 3) / 6;
-    int a[NTAB][3];
-    constexpr TensorAlpha() : a{} {
-        int t = 0;
-        for (int k = 0; k <= ORDER; ++k) {
-            if (NF == 2) {
-                for (int i = 0; i <= k; ++i) {
-                    a[t][0] = k - i;
-                    a[t][1] = i;
-                    a[t][2] = 0;
-                    ++t;
-                }
-            } else {
-                for (int i = 0; i <= k; ++i)
-                    for (int j = 0; j <= i; ++j) {
-                        a[t][0] = k - i;
-                        a[t][1] = i - j;
-                        a[t][2] = j;
-                        ++t;
-                    }
-            }
-        }
-    }
-};
-
 template <int NF, int NN, int ORDER, bool GRID>
 __global__ __launch_bounds__(256) void tensor_small_kernel(const TensorArgs a, const int P, const int img_doubles) {
     static_assert(NF == 2 || NF == 3, "two or three interval factors");

@@ -554,3 +554,66 @@ def tensor_tabulate_batch(factors, order, pts, out=None, stream=None, grid=False
         check(lib.fx_tensor_tabulate_batch(ctx.handle, nf, arr, int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out),
                                            _stream_ptr(stream)))
     return out
+
+
+HDIV, HCURL = 0, 1          # include/fiat_amd.h FX_HDIV / FX_HCURL
+
+
+def hdivcurl_tabulate_batch(sd, kind, C, D, offsets, signs, order, pts, out=None, stream=None, grid=False):
+    """H(div) / H(curl) elements of quadrilaterals and hexahedra on the fused kernel (fx_hdivcurl_tabulate_batch): ``C``,
+    ``D`` LineLagrange factors of K+1 and K nodes, ``offsets[c]`` the first dof of component c's block (-1: none),
+    ``signs[c]`` its sign.  grid=False: pts (nreq, npts, sd); grid=True: pts (nreq, sd, q) 1-D coordinates.  ->
+    (nreq, ntab, ndof, sd, npts) on the device, or None when the shape has no instance (the caller takes the general route)."""
+    ctx = C.ctx
+    pts = _as_device(pts, ctx)
+    if grid:
+        if pts.dim() != 3 or pts.shape[1] != sd:
+            raise ValueError(f"grid coordinates must have shape (nreq, {sd}, q), got {tuple(pts.shape)}")
+        nreq, q = int(pts.shape[0]), int(pts.shape[2])
+        npts = q ** sd
+    else:
+        if pts.dim() != 3 or pts.shape[2] != sd:
+            raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+        nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    offs = np.ascontiguousarray(offsets, dtype=np.int32)
+    sgn = np.ascontiguousarray(signs, dtype=np.int32)
+    if offs.shape != (sd,) or sgn.shape != (sd,):
+        raise ValueError("offsets and signs need one entry per component")
+    K = D.nn
+    nb = (K + 1) * K ** (sd - 1) if kind == HDIV else K * (K + 1) ** (sd - 1)
+    shape = (nreq, num_tables(sd, order), nb * int((offs >= 0).sum()), sd, npts)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out has the wrong shape/dtype/layout")
+    if grid:
+        rc = lib.fx_hdivcurl_tabulate_grid_batch(ctx.handle, int(sd), int(kind), C.handle, D.handle, host_ptr(offs),
+                                                 host_ptr(sgn), int(order), nreq, q, _dev_ptr(pts), _dev_ptr(out),
+                                                 _stream_ptr(stream))
+    else:
+        rc = lib.fx_hdivcurl_tabulate_batch(ctx.handle, int(sd), int(kind), C.handle, D.handle, host_ptr(offs), host_ptr(sgn),
+                                            int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream))
+    if rc == _lib.FX_ENOTIMPL:
+        return None
+    check(rc)
+    return out
+
+
+def table_place(src, dst, row_offset, comp_src, comp_sign, ctx=None, stream=None):
+    """The general route's placement pass (fx_table_place_batch): src (nreq, ntab, rows, *value_shape, npts) into the rows
+    [row_offset, row_offset + rows) of dst (nreq, ntab, rows_dst, *value_shape_dst, npts); component c of dst is
+    comp_sign[c] * component comp_src[c] of src, or zero where comp_src[c] < 0."""
+    ctx = ctx or Context.get()
+    src = _as_device(src, ctx)
+    nreq, ntab, rows, npts = int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), int(src.shape[-1])
+    vdim_src = int(np.prod(src.shape[3:-1], dtype=np.int64))
+    vdim_dst = int(np.prod(dst.shape[3:-1], dtype=np.int64))
+    if (dst.shape[0], dst.shape[1], dst.shape[-1]) != (nreq, ntab, npts) or not dst.is_contiguous() or dst.dtype != torch.float64:
+        raise ValueError("dst must share the request, table and point axes of src (contiguous float64)")
+    comp = np.ascontiguousarray(comp_src, dtype=np.int32)
+    sgn = np.ascontiguousarray(comp_sign, dtype=np.int32)
+    if comp.shape != (vdim_dst,) or sgn.shape != (vdim_dst,):
+        raise ValueError("one source component and sign per component of dst")
+    check(lib.fx_table_place_batch(ctx.handle, ntab, nreq, npts, rows, vdim_src, _dev_ptr(src), int(dst.shape[2]), vdim_dst,
+                                   int(row_offset), host_ptr(comp), host_ptr(sgn), _dev_ptr(dst), _stream_ptr(stream)))
+    return dst

@@ -13,6 +13,7 @@ coordinates); every other product tabulates its two factors with their own kerne
 import numpy
 
 from . import runtime
+from .enriched import EnrichedElement
 from .polynomial_set_util import mis
 from .reference_element import LINE, TensorProductCell
 
@@ -22,7 +23,7 @@ def _first_point(node):
 
 
 def _is_line_lagrange(element):
-    if isinstance(element, (TensorProductElement, FlattenedDimensions)):
+    if isinstance(element, (TensorProductElement, FlattenedDimensions, EnrichedElement)):
         return False
     es = element.get_nodal_basis().get_expansion_set()
     return element.get_reference_element().get_shape() == LINE and hasattr(es, "device_line") and element.value_shape() == ()
@@ -33,6 +34,8 @@ def _line_factors(element):
     if isinstance(element, FlattenedDimensions):
         return _line_factors(element.element)
     if isinstance(element, TensorProductElement):
+        if element.value_shape() != ():                                 # Hdiv / Hcurl: a vector field, not a scalar product
+            return None
         left, right = _line_factors(element.A), _line_factors(element.B)
         return None if left is None or right is None else left + right
     return [element] if _is_line_lagrange(element) else None
@@ -183,15 +186,41 @@ class TensorProductElement:
         return {a: numpy.ascontiguousarray(host[t]) for t, a in enumerate(keys)}
 
     def dual_basis(self):
-        """Point evaluations at the concatenated nodes for products of point-evaluation factors
-        (FIAT/tensor_product.py:70-190, scalar x scalar case)."""
-        from . import functional
+        """The product's nodes, case by case as FIAT/tensor_product.py:70-205: point evaluations at the concatenated points
+        for products of point evaluations, component point evaluations for (component point evaluation) x (point
+        evaluation), typed functionals for the vector-valued and integral-moment cases, undefined functionals otherwise."""
+        from . import functional as fn
+        sd = self.ref_el.get_spatial_dimension()
+        undefined = lambda: fn.Functional(None, None, None, {}, "Undefined")   # noqa: E731
         nodes = []
         for na in self.A.dual_basis():
             for nb in self.B.dual_basis():
-                if not (isinstance(na, functional.PointEvaluation) and isinstance(nb, functional.PointEvaluation)):
-                    raise NotImplementedError("dual basis of products of non-point-evaluation factors")
-                nodes.append(functional.PointEvaluation(self.ref_el, _first_point(na) + _first_point(nb)))
+                b_point = isinstance(nb, fn.PointEvaluation)
+                if isinstance(na, fn.PointEvaluation):
+                    if b_point:
+                        nodes.append(fn.PointEvaluation(self.ref_el, _first_point(na) + _first_point(nb)))
+                    elif isinstance(nb, (fn.IntegralMoment, fn.PointDerivative)):
+                        nodes.append(undefined())
+                    else:
+                        raise NotImplementedError("unsupported functional type")
+                elif isinstance(na, (fn.PointScaledNormalEvaluation, fn.PointEdgeTangentEvaluation)):
+                    if not b_point:
+                        raise NotImplementedError("unsupported functional type")
+                    (pa, va), = na.get_point_dict().items()
+                    tag = "PointScaledNormalEval" if isinstance(na, fn.PointScaledNormalEvaluation) else "PointEdgeTangent"
+                    nodes.append(fn.Functional(self.ref_el, (sd,), {pa + _first_point(nb): va + [(0.0, (len(pa),))]}, {}, tag))
+                elif isinstance(na, fn.ComponentPointEvaluation):
+                    if not b_point:
+                        raise NotImplementedError("unsupported functional type")
+                    nodes.append(fn.ComponentPointEvaluation(self.ref_el, na.comp, (sd,), _first_point(na) + _first_point(nb)))
+                elif isinstance(na, fn.IntegralMoment):
+                    if not b_point:
+                        raise NotImplementedError("unsupported functional type")
+                    frob = isinstance(na, fn.FrobeniusIntegralMoment)
+                    pt_dict = {pt + _first_point(nb): (wc + [(0.0, sd - 1)] if frob else wc) for pt, wc in na.get_point_dict().items()}
+                    nodes.append(fn.Functional(self.ref_el, (sd,), pt_dict, {}, "FrobeniusIntegralMoment" if frob else "IntegralMoment"))
+                else:
+                    nodes.append(undefined())
         return nodes
 
 

@@ -383,6 +383,30 @@ int fx_bernstein_tabulate_batch(fx_ctx* ctx, int sd, int n, const double* cell, 
 int fx_bernstein_tabulate_shared(fx_ctx* ctx, int sd, int n, const double* cell, int order, int64_t nreq, int npts,
                                  const double* ref_pts, const double* verts, double* out, void* stream);
 
+/* ---- H(div) / H(curl) tensor-product elements (FIAT/hdivcurl.py, FIAT/enriched.py) -------------------------
+ * The fused route for RTCF / RTCE / NCF / NCE and their single summands on quadrilaterals (sd 2) and hexahedra (sd 3).
+ * The element is described by its BLOCKS: block c (offset[c] >= 0) is the product over the directions d of C (K+1 nodes)
+ * or D (K nodes) -- FX_HDIV: C where d == c, FX_HCURL: D where d == c --, its dofs the range offset[c] + (row-major index
+ * over (x, y[, z])), placed into component c with the factor sign[c] (+1 or -1), zeros in the other components.  The
+ * blocks must tile [0, ndof), ndof = (number of blocks) * (block size).  pts device [nreq][npts][sd] (grid: [nreq][sd][q],
+ * npts = q^sd); out device [nreq][ntab][ndof][sd][npts].  Instances: K = 1..4 (sd 2), 1..3 (sd 3), order <= 2; other shapes
+ * return FX_ENOTIMPL (the caller takes the general route), bad descriptors FX_EINVAL. */
+#define FX_HDIV 0
+#define FX_HCURL 1
+int fx_hdivcurl_tabulate_batch(fx_ctx* ctx, int sd, int kind, const fx_line_element* C, const fx_line_element* D,
+                               const int* offset, const int* sign, int order, int64_t nreq, int npts, const double* pts,
+                               double* out, void* stream);
+int fx_hdivcurl_tabulate_grid_batch(fx_ctx* ctx, int sd, int kind, const fx_line_element* C, const fx_line_element* D,
+                                    const int* offset, const int* sign, int order, int64_t nreq, int q, const double* grid,
+                                    double* out, void* stream);
+/* The general route's placement pass: src device [nreq][ntab][rows_src][vdim_src][npts] (one leaf of the composition) into
+ * the rows [row_offset, row_offset + rows_src) of dst device [nreq][ntab][rows_dst][vdim_dst][npts]: component c of dst is
+ * comp_sign[c] * component comp_src[c] of src, or 0 where comp_src[c] < 0 (host arrays of vdim_dst entries; 1..9 components).
+ * Every component of those rows is written. */
+int fx_table_place_batch(fx_ctx* ctx, int ntab, int64_t nreq, int npts, int rows_src, int vdim_src, const double* src,
+                         int rows_dst, int vdim_dst, int row_offset, const int* comp_src, const int* comp_sign, double* dst,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
