@@ -1213,15 +1213,18 @@ const CoopShape kCoopShapes[] = {
                              // Piola map fuses into this kernel's output rounds (generic + second pass: 616 us)
 };
 
-template <int SD, int ORDER, int MT16, int M4, int TPW, bool CAN_PIOLA = false>
+template <int SD, int ORDER, int MT16, int M4, int TPW, bool CAN_PIOLA = false, bool PIOLA_ONLY = false>
 int launch_coop(const Launch& L, hipStream_t s) {
     using KernT = void (*)(const fxk::CoopArgs);
-    KernT kern = L.cargs.verts ? (KernT)fxk::tabulate_simplex_coop<SD, ORDER, MT16, M4, TPW, false>
-                               : (KernT)fxk::tabulate_simplex_coop<SD, ORDER, MT16, M4, TPW, true>;
+    KernT kern = nullptr;
+    if constexpr (!PIOLA_ONLY)   // (a shape registered for fused launches only -- CoopShape::piola_only -- has no other twin)
+        kern = L.cargs.verts ? (KernT)fxk::tabulate_simplex_coop<SD, ORDER, MT16, M4, TPW, false>
+                             : (KernT)fxk::tabulate_simplex_coop<SD, ORDER, MT16, M4, TPW, true>;
     if (L.cargs.piola) {
         if constexpr (CAN_PIOLA) kern = (KernT)fxk::tabulate_simplex_coop<SD, ORDER, MT16, M4, TPW, false, true>;
         else return fail(FX_EINVAL, "internal: no fused push-forward for this cooperative shape");
     }
+    if (!kern) return fail(FX_EINVAL, "internal: this cooperative shape only fuses a push-forward");
     if (L.clds_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     L.clds_bytes));
@@ -1235,7 +1238,7 @@ int run_coop(const Launch& L, hipStream_t s) {
         case 0: return launch_coop<3, 2, 5, 1, 4>(L, s);
         case 1: return launch_coop<3, 1, 5, 1, 2>(L, s);
         case 2: return launch_coop<3, 1, 3, 3, 2, true>(L, s);
-        case 3: return launch_coop<3, 1, 3, 0, 2, true>(L, s);
+        case 3: return launch_coop<3, 1, 3, 0, 2, true, true>(L, s);
     }
     return fail(FX_EINVAL, "internal: unknown cooperative kernel %d", L.coop_id);
 }
@@ -1358,9 +1361,11 @@ int launch_sd(int order, const Launch& L, hipStream_t s) {
         case 0:
             return launch_one<SD, 0, 0, 0>(L, s);
         case 1:
-            if (SD == 3 && KS == 5 && MT == 2) return launch_one<SD, 1, 5, 2>(L, s);  // P3 tet
-            if (SD == 3 && KS == 3 && MT == 4) return launch_one<SD, 1, 3, 4>(L, s);  // N2 tet
-            if (SD == 3 && KS == 3 && MT == 3) return launch_one<SD, 1, 3, 3>(L, s);  // RT2 tet
+            if constexpr (SD == 3) {  // (tetrahedra only: no instance of these three is compiled for SD 1 and 2)
+                if (KS == 5 && MT == 2) return launch_one<SD, 1, 5, 2>(L, s);  // P3 tet
+                if (KS == 3 && MT == 4) return launch_one<SD, 1, 3, 4>(L, s);  // N2 tet
+                if (KS == 3 && MT == 3) return launch_one<SD, 1, 3, 3>(L, s);  // RT2 tet
+            }
             return launch_one<SD, 1, 0, 0>(L, s);
         case 2:
             return launch_one<SD, 2, 0, 0>(L, s);
@@ -1921,7 +1926,9 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                         if (wg_ctw == 7) wg_ctw = 8;        // (no seven-tile instance)
                         if (wg_ctw == 5) {                   // one wave per row tile on 5 column tiles, or two on 3 + 3: the fewer MFMA slots per wave
                             const long long one = (long long)((RT + 3) / 4) * 5, two = (long long)((RT + 1) / 2) * 3;
-                            if (two < one) wg_ctw = 6;
+                            // (the one-wave-per-row-tile layout holds ONE request per slab: twelve requests of 6 points -- policy
+                            // wg_small, 72 columns -- were planned onto it and refused by the launch, hipErrorInvalidValue)
+                            if (two < one || wg_g > 1) wg_ctw = 6;
                         }
                         // (... except the instances of one wave per row tile on five column tiles, since the recurrence coefficients are
                         // fetched ahead and the last tile of a group leaves under the next group's MFMAs (second half of round 4;
@@ -2163,16 +2170,31 @@ int launch_shared(int order, const fxk::SharedArgs& sa, int ncu, hipStream_t s, 
     if (!noreg && (sa.kind == 0 || sa.vdim == SD)) {
         const bool piola = sa.kind != 0;
         bool ok = false;
+        // (Piola instances: none for SD 1 -- the entry refuses the map there -- and none with odd tables for SD 2, where a table
+        // has 2 ndof rows; fx_tabulate_batch_shared never asks for either)
+        constexpr bool PIO_EVEN = SD >= 2, PIO_ODD = SD == 3;
         if (table & 1) {
-            if (order == 0) ok = piola ? launch_shared_reg_sliced<SD, 0, true, 1>(table, sa, ncu, s) : launch_shared_reg_sliced<SD, 0, false, 1>(table, sa, ncu, s);
-            if (order == 1) ok = piola ? launch_shared_reg_sliced<SD, 1, true, 1>(table, sa, ncu, s) : launch_shared_reg_sliced<SD, 1, false, 1>(table, sa, ncu, s);
-            // (odd tables with Hessians -- N3 / RT2 tetrahedra, P5 triangles at their default rules -- ran on the
-            // one-workgroup-per-request fallback at 1-20 % of the HBM peak: tools/coverage_map_cells.py)
-            if (order == 2) ok = piola ? launch_shared_reg_sliced<SD, 2, true, 1>(table, sa, ncu, s) : launch_shared_reg_sliced<SD, 2, false, 1>(table, sa, ncu, s);
+            if (!piola) {
+                if (order == 0) ok = launch_shared_reg_sliced<SD, 0, false, 1>(table, sa, ncu, s);
+                if (order == 1) ok = launch_shared_reg_sliced<SD, 1, false, 1>(table, sa, ncu, s);
+                // (odd tables with Hessians -- N3 / RT2 tetrahedra, P5 triangles at their default rules -- ran on the
+                // one-workgroup-per-request fallback at 1-20 % of the HBM peak: tools/coverage_map_cells.py)
+                if (order == 2) ok = launch_shared_reg_sliced<SD, 2, false, 1>(table, sa, ncu, s);
+            } else if constexpr (PIO_ODD) {
+                if (order == 0) ok = launch_shared_reg_sliced<SD, 0, true, 1>(table, sa, ncu, s);
+                if (order == 1) ok = launch_shared_reg_sliced<SD, 1, true, 1>(table, sa, ncu, s);
+                if (order == 2) ok = launch_shared_reg_sliced<SD, 2, true, 1>(table, sa, ncu, s);
+            }
         } else {
-            if (order == 0) ok = piola ? launch_shared_reg_sliced<SD, 0, true, 2>(table / 2, sa, ncu, s) : launch_shared_reg_sliced<SD, 0, false, 2>(table / 2, sa, ncu, s);
-            if (order == 1) ok = piola ? launch_shared_reg_sliced<SD, 1, true, 2>(table / 2, sa, ncu, s) : launch_shared_reg_sliced<SD, 1, false, 2>(table / 2, sa, ncu, s);
-            if (order == 2) ok = piola ? launch_shared_reg_sliced<SD, 2, true, 2>(table / 2, sa, ncu, s) : launch_shared_reg_sliced<SD, 2, false, 2>(table / 2, sa, ncu, s);
+            if (!piola) {
+                if (order == 0) ok = launch_shared_reg_sliced<SD, 0, false, 2>(table / 2, sa, ncu, s);
+                if (order == 1) ok = launch_shared_reg_sliced<SD, 1, false, 2>(table / 2, sa, ncu, s);
+                if (order == 2) ok = launch_shared_reg_sliced<SD, 2, false, 2>(table / 2, sa, ncu, s);
+            } else if constexpr (PIO_EVEN) {
+                if (order == 0) ok = launch_shared_reg_sliced<SD, 0, true, 2>(table / 2, sa, ncu, s);
+                if (order == 1) ok = launch_shared_reg_sliced<SD, 1, true, 2>(table / 2, sa, ncu, s);
+                if (order == 2) ok = launch_shared_reg_sliced<SD, 2, true, 2>(table / 2, sa, ncu, s);
+            }
         }
         if (ok) {
             HIP_TRY(hipGetLastError());

@@ -418,6 +418,32 @@ def check_guarded(buf, out):
     assert not bool(torch.isnan(out).any()), "NaN in out"
 
 
+def launched(call):
+    """Names of the device kernels that ``call`` launches (the profiler's device-side records)."""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        call()
+        torch.cuda.synchronize()
+    return {e.name for e in prof.events() if e.device_type.name == "CUDA" and "Memcpy" not in e.name and "Memset" not in e.name}
+
+
+def compare(call, shape, device):
+    """call(out) for a fresh out and for guarded views at every offset."""
+    import torch
+    fresh = torch.empty(shape, dtype=torch.float64, device=device)
+    call(fresh)
+    torch.cuda.synchronize()
+    for off in OFFSETS:
+        buf, out = guarded_out(shape, off, device)
+        call(out)
+        torch.cuda.synchronize()
+        check_guarded(buf, out)
+        assert torch.equal(out, fresh), off
+    return fresh
+
+
 def rel_to_exact(approx, exact):
     """max |approx - exact| / max(1, max |exact|) over nested lists of long doubles and Fractions, computed exactly."""
     a = np.asarray(approx, dtype=LD).ravel()

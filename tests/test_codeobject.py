@@ -47,3 +47,27 @@ def test_scratch_budget(report):
     assert worst["scratch"] <= SCRATCH_BUDGET, worst
     # ... and few kernels use any: 17 of 583 at the end of round 3 (was 9 of 332), all <= 96 B
     assert sum(1 for k in kernels if k["scratch"]) <= max(16, len(kernels) // 30)
+
+
+@pytest.fixture(scope="module")
+def report_all():
+    import codeobject_report
+    return codeobject_report.kernels(all_units=True)
+
+
+# The report above reads api.hip's code object, the first of four in the library, and so does the budget; wg.hip,
+# bernstein.hip and hdivcurl.hip were never held against it.  Three instances of the request-per-workgroup kernel are above
+# it (408, 368 and 132 B per lane): each is reached by a checked case of tests/instance_manifest.py, and they are pinned
+# here by name so that no further one joins them unseen.
+OVER_BUDGET_ELSEWHERE = {"fxk::tabulate_simplex_wg<3,6,5,false,1,0,true>", "fxk::tabulate_simplex_wg<3,5,6,true,2,1,false>",
+                         "fxk::tabulate_simplex_wg<3,4,5,false,1,0,true>"}
+
+
+def test_scratch_budget_of_the_other_translation_units(report_all):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import instance_manifest
+    kernels, _ = report_all
+    rest = [k for k in kernels if k["unit"] > 0]
+    assert len(rest) > 200          # wg.hip, bernstein.hip, hdivcurl.hip are in the report
+    over = [k for k in rest if k["scratch"] > SCRATCH_BUDGET]
+    assert set(instance_manifest.normalise_all([k["name"] for k in over])) <= OVER_BUDGET_ELSEWHERE, over

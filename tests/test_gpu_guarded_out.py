@@ -17,38 +17,13 @@ import edge_reference as R  # noqa: E402
 import make_golden_hdivcurl as M  # noqa: E402
 
 BERN, HDC = R.GUARD_BERN, R.GUARD_HDC          # shape lists of edge_reference.py (the host test checks their routes)
-
-
-def launched(call):
-    """Names of the device kernels that ``call`` launches (the profiler's device-side records)."""
-    import torch
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        call()
-        torch.cuda.synchronize()
-    return {e.name for e in prof.events() if e.device_type.name == "CUDA" and "Memcpy" not in e.name and "Memset" not in e.name}
+launched, compare = R.launched, R.compare      # (shared with tests/test_gpu_instances.py)
 
 
 def only_kernel(names, family):
     """Exactly one kernel of the call is of ``family`` (a name such as "fxk::tensor_small_kernel")."""
     hits = [n for n in names if family + "<" in n]
     assert len(hits) == 1, (family, sorted(names))
-
-
-def compare(call, shape, device):
-    """call(out) for a fresh out and for guarded views at every offset."""
-    import torch
-    fresh = torch.empty(shape, dtype=torch.float64, device=device)
-    call(fresh)
-    torch.cuda.synchronize()
-    for off in R.OFFSETS:
-        buf, out = R.guarded_out(shape, off, device)
-        call(out)
-        torch.cuda.synchronize()
-        R.check_guarded(buf, out)
-        assert torch.equal(out, fresh), off
-    return fresh
 
 
 def pts_simplex(rng, nreq, npts, sd):
