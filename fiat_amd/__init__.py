@@ -38,6 +38,7 @@ from .tensor_product import FlattenedDimensions, TensorProductElement  # noqa: F
 from .bernstein import Bernstein  # noqa: F401
 from .enriched import EnrichedElement  # noqa: F401
 from .hdivcurl import Hcurl, Hdiv  # noqa: F401
+from .serendipity import Serendipity  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
@@ -58,6 +59,7 @@ supported_elements = {
     "TensorProductElement": TensorProductElement,
     "FlattenedDimensions": FlattenedDimensions,
     "Bernstein": Bernstein,
+    "S": Serendipity,
 }
 
 # (FIAT/__init__.py:130-131)

@@ -121,12 +121,52 @@ for _name, (_res, _args) in _SIGS.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# The Serendipity kernels live in a companion library (include/fiat_amd_serendipity.h), built beside the default main
+# library and linked against it: it is loaded after the main one so that both share one error slot and the contexts.
+# Under a FIAT_AMD_LIB override the companion still resolves the default libfiat_amd.so of its own directory.  No
+# fallback: a missing companion fails the import.
+SER_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_serendipity.so")
+if not os.path.exists(SER_LIB_PATH):
+    raise ImportError(
+        f"{SER_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
 
-def check(rc):
-    """Map C status codes to the exception types the reference raises."""
+serlib = ctypes.CDLL(SER_LIB_PATH)
+
+_SER_SIGS = {
+    "fx_serendipity_abi_version": (c_int, []),
+    "fx_serendipity_dims": (c_int, [c_int, c_int, _p_i]),
+    "fx_serendipity_descriptor": (c_int, [c_int, c_int, c_void_p]),
+    "fx_serendipity_kernel": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_serendipity_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                              c_void_p, c_void_p]),
+}
+
+SER_EXPORTS = tuple(_SER_SIGS)
+
+for _name, (_res, _args) in _SER_SIGS.items():
+    _fn = getattr(serlib, _name)       # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+# the main library the companion is linked against (its error slot): ``lib`` itself unless FIAT_AMD_LIB overrides that
+_DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd.so")
+_ser_main = lib if os.path.realpath(LIB_PATH) == os.path.realpath(_DEFAULT_LIB_PATH) else ctypes.CDLL(_DEFAULT_LIB_PATH)
+_ser_main.fx_last_error.restype = c_char_p
+_ser_main.fx_last_error.argtypes = []
+
+
+def ser_check(rc):
+    """``check`` for the companion's entries."""
+    return check(rc, _ser_main)
+
+
+def check(rc, errlib=None):
+    """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the
+    text; default: the main library)."""
     if rc >= 0:
         return rc
-    msg = lib.fx_last_error().decode()
+    msg = (errlib or lib).fx_last_error().decode()
     if rc == FX_EINVAL:
         raise ValueError(msg)
     if rc == FX_ENOTIMPL:

@@ -617,3 +617,48 @@ def table_place(src, dst, row_offset, comp_src, comp_sign, ctx=None, stream=None
     check(lib.fx_table_place_batch(ctx.handle, ntab, nreq, npts, rows, vdim_src, _dev_ptr(src), int(dst.shape[2]), vdim_dst,
                                    int(row_offset), host_ptr(comp), host_ptr(sgn), _dev_ptr(dst), _stream_ptr(stream)))
     return dst
+
+
+def serendipity_descriptor(sd, degree):
+    """The dof table of S_degree the kernels are compiled from (fx_serendipity_descriptor; host only): rows (sign, code_x,
+    code_y[, code_z])."""
+    ndof = c_int(0)
+    _lib.ser_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
+    rows = np.zeros((ndof.value, 1 + sd), dtype=np.int32)
+    _lib.ser_check(_lib.serlib.fx_serendipity_descriptor(int(sd), int(degree), host_ptr(rows)))
+    return rows
+
+
+def serendipity_kernel(sd, degree, order, npts):
+    """Name of the kernel instance and output route a shape takes (fx_serendipity_kernel; host only)."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.serlib.fx_serendipity_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
+    return buf.value.decode()
+
+
+def serendipity_tabulate_batch(sd, degree, lo, hi, order, pts, out=None, stream=None, ctx=None):
+    """Serendipity S_degree on the box [lo, hi] (fx_serendipity_tabulate_batch): pts (nreq, npts, sd) -> (nreq, ntab,
+    ndof, npts) on the device.  Shapes beyond the generic instance raise NotImplementedError; there is no other route."""
+    ctx = ctx or Context.get()
+    pts = _as_device(pts, ctx)
+    if pts.dim() != 3 or pts.shape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1)
+    if lo.shape != (sd,) or hi.shape != (sd,):
+        raise ValueError("the box needs one lower and one upper coordinate per direction")
+    ndof = c_int(0)
+    _lib.ser_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
+    if order < 0:
+        raise ValueError("negative derivative order")
+    shape = (nreq, num_tables(sd, order), ndof.value, npts)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        serendipity_kernel(sd, degree, order, npts)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.serlib.fx_serendipity_tabulate_batch(ctx.handle, int(sd), int(degree), host_ptr(lo), host_ptr(hi), int(order),
+                                                    nreq, npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    return out
