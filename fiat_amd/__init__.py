@@ -39,6 +39,10 @@ from .bernstein import Bernstein  # noqa: F401
 from .enriched import EnrichedElement  # noqa: F401
 from .hdivcurl import Hcurl, Hdiv  # noqa: F401
 from .serendipity import Serendipity  # noqa: F401
+from .brezzi_douglas_marini_cube import BrezziDouglasMariniCubeEdge, BrezziDouglasMariniCubeFace  # noqa: F401
+from .Sminus import TrimmedSerendipityEdge, TrimmedSerendipityFace  # noqa: F401
+from .SminusCurl import TrimmedSerendipityCurl  # noqa: F401
+from .SminusDiv import TrimmedSerendipityDiv  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
@@ -60,6 +64,12 @@ supported_elements = {
     "FlattenedDimensions": FlattenedDimensions,
     "Bernstein": Bernstein,
     "S": Serendipity,
+    "Brezzi-Douglas-Marini Cube Edge": BrezziDouglasMariniCubeEdge,
+    "Brezzi-Douglas-Marini Cube Face": BrezziDouglasMariniCubeFace,
+    "SminusE": TrimmedSerendipityEdge,
+    "SminusF": TrimmedSerendipityFace,
+    "SminusCurl": TrimmedSerendipityCurl,
+    "SminusDiv": TrimmedSerendipityDiv,
 }
 
 # (FIAT/__init__.py:130-131)

@@ -161,6 +161,33 @@ def ser_check(rc):
     return check(rc, _ser_main)
 
 
+# The term-table kernel of BDMCE / BDMCF and the trimmed serendipity families is a second companion library
+# (include/fiat_amd_sforms.h), loaded and bound like the first.  No fallback: a missing companion fails the import.
+SF_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_sforms.so")
+if not os.path.exists(SF_LIB_PATH):
+    raise ImportError(
+        f"{SF_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+
+sflib = ctypes.CDLL(SF_LIB_PATH)
+
+_SF_SIGS = {
+    "fx_sforms_abi_version": (c_int, []),
+    "fx_sforms_element_create": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "fx_sforms_element_destroy": (c_int, [c_void_p]),
+    "fx_sforms_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_sforms_tabulate_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                         c_void_p]),
+}
+
+SF_EXPORTS = tuple(_SF_SIGS)
+
+for _name, (_res, _args) in _SF_SIGS.items():
+    _fn = getattr(sflib, _name)        # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+
 def check(rc, errlib=None):
     """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the
     text; default: the main library)."""

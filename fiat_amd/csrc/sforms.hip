@@ -1,0 +1,203 @@
+// Host side of the term-table kernel (sforms.hpp): libfiat_amd_sforms.so, a companion of libfiat_amd.so
+// (include/fiat_amd_sforms.h).  It links against the main library and uses its error slot and contexts.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/fiat_amd_sforms.h"
+#include "sforms.hpp"
+
+namespace fx {
+int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
+void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
+}  // namespace fx
+
+struct fx_sforms_element {
+    int device, sd, degree, nrows;
+    double* coef;  // device [nrows * sd]
+    int* codes;    // device [nrows * sd]
+};
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return fx::set_error(code, buf);
+}
+
+#define SF_HIP_TRY(expr)                                                          \
+    do {                                                                          \
+        hipError_t e_ = (expr);                                                   \
+        if (e_ != hipSuccess) {                                                   \
+            (void)hipGetLastError();                                              \
+            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
+        }                                                                         \
+    } while (0)
+
+// which route a shape takes
+struct SfPlan {
+    int P, image, ntab, budget;
+    long long reqsize;
+    size_t lds;
+};
+
+int check_shape(const char* who, int sd, int degree, int nrows) {
+    if (sd != 2 && sd != 3) return fail(FX_EINVAL, "%s: spatial dimension %d (quadrilaterals and hexahedra)", who, sd);
+    if (degree < 1) return fail(FX_EINVAL, "%s: degree %d (>= 1)", who, degree);
+    if (degree > fxk::SF_MAXK) return fail(FX_ENOTIMPL, "%s: degree %d > %d", who, degree, fxk::SF_MAXK);
+    if (nrows < 1) return fail(FX_EINVAL, "%s: %d rows", who, nrows);
+    return FX_OK;
+}
+
+int make_plan(const char* who, int sd, int degree, int nrows, int order, int npts, SfPlan* p) {
+    const int rc = check_shape(who, sd, degree, nrows);
+    if (rc != FX_OK) return rc;
+    if (order < 0 || npts < 0) return fail(FX_EINVAL, "%s: negative order or count", who);
+    if (order > fxk::SF_MAXORDER) return fail(FX_ENOTIMPL, "%s: derivative order %d > %d", who, order, fxk::SF_MAXORDER);
+    p->ntab = (int)(sd == 2 ? (order + 1) * (order + 2) / 2 : (order + 1) * (order + 2) * (order + 3) / 6);
+    p->reqsize = (long long)p->ntab * nrows * sd * npts;
+    if (p->reqsize >= (1LL << 31)) return fail(FX_ENOTIMPL, "%s: request of %lld entries", who, p->reqsize);
+    p->budget = fxk::sf_image_budget(sd, degree, order);
+    p->P = npts > 0 && npts <= 64 ? 64 / npts : 1;  // whole requests per 64 lanes
+    p->image = 0;
+    p->lds = fxk::sf_tables_bytes(sd, degree, order);
+    if (p->reqsize > 0 && p->reqsize * 8 <= p->budget) {
+        // the item shrinks to the requests whose tables fit the image
+        p->image = 1;
+        p->P = (int)std::min<long long>(p->P, p->budget / (p->reqsize * 8));
+        p->lds += (size_t)(((long long)p->P * p->reqsize + 1) & ~1LL) * 8;
+    }
+    return FX_OK;
+}
+
+template <int SD, int ORDER> hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::SfArgs& a) {
+    auto kern = fxk::sforms_kernel<SD, ORDER>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
+    return hipGetLastError();
+}
+
+template <int SD> hipError_t launch_order(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::SfArgs& a) {
+    if (order == 0) return launch_one<SD, 0>(grid, lds, s, a);
+    if (order == 1) return launch_one<SD, 1>(grid, lds, s, a);
+    return launch_one<SD, 2>(grid, lds, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fx_sforms_abi_version(void) { return 1; }
+
+int fx_sforms_element_create(fx_ctx* ctx, int sd, int degree, int nrows, const double* coef, const int* codes,
+                             fx_sforms_element** out) {
+    const char* who = "fx_sforms_element_create";
+    if (!ctx || !coef || !codes || !out) return fail(FX_EINVAL, "%s: null argument", who);
+    const int rc = check_shape(who, sd, degree, nrows);
+    if (rc != FX_OK) return rc;
+    if ((long long)nrows * sd >= (1LL << 24)) return fail(FX_ENOTIMPL, "%s: %d rows", who, nrows);
+    const int nf = fxk::sf_ncodes(degree);
+    const size_t n = (size_t)nrows * sd;
+    const size_t npad = (n + fxk::SF_CHUNK - 1) / fxk::SF_CHUNK * fxk::SF_CHUNK;  // the kernel fetches whole chunks
+    std::vector<int> packed(npad, 0);
+    std::vector<double> padded(npad, 0.0);
+    std::copy(coef, coef + n, padded.begin());
+    for (size_t e = 0; e < n; ++e) {
+        if (!(coef[e] == coef[e]) || coef[e] - coef[e] != 0.0) return fail(FX_EINVAL, "%s: entry %zu: coefficient not finite", who, e);
+        if (coef[e] == 0.0) continue;
+        int c[3] = {0, 0, 0};
+        for (int d = 0; d < sd; ++d) {
+            c[d] = codes[e * sd + d];
+            if (c[d] < 0 || c[d] >= nf) return fail(FX_EINVAL, "%s: entry %zu: code %d outside the 1-D family (0..%d)", who, e, c[d], nf - 1);
+        }
+        packed[e] = fxk::sf_pack(c[0], c[1], c[2]);
+    }
+    int device = 0, num_cu = 0, lds_per_cu = 0;
+    fx::ctx_facts(ctx, &device, &num_cu, &lds_per_cu);
+    SF_HIP_TRY(hipSetDevice(device));
+    fx_sforms_element* el = new fx_sforms_element{device, sd, degree, nrows, nullptr, nullptr};
+    hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&el->coef), npad * sizeof(double));
+    hipError_t e2 = e1 == hipSuccess ? hipMalloc(reinterpret_cast<void**>(&el->codes), npad * sizeof(int)) : e1;
+    if (e2 == hipSuccess) e2 = hipMemcpy(el->coef, padded.data(), npad * sizeof(double), hipMemcpyHostToDevice);
+    if (e2 == hipSuccess) e2 = hipMemcpy(el->codes, packed.data(), npad * sizeof(int), hipMemcpyHostToDevice);
+    if (e2 != hipSuccess) {
+        (void)hipGetLastError();
+        if (el->coef) (void)hipFree(el->coef);
+        if (el->codes) (void)hipFree(el->codes);
+        delete el;
+        return fail(e2 == hipErrorOutOfMemory ? FX_ENOMEM : FX_EHIP, "%s: %s", who, hipGetErrorString(e2));
+    }
+    *out = el;
+    return FX_OK;
+}
+
+int fx_sforms_element_destroy(fx_sforms_element* el) {
+    if (!el) return FX_OK;
+    (void)hipFree(el->coef);
+    (void)hipFree(el->codes);
+    delete el;
+    return FX_OK;
+}
+
+int fx_sforms_kernel(int sd, int degree, int nrows, int order, int npts, char* buf, int n) {
+    if (!buf || n <= 0) return fail(FX_EINVAL, "fx_sforms_kernel: no buffer");
+    SfPlan p;
+    const int rc = make_plan("fx_sforms_kernel", sd, degree, nrows, order, npts, &p);
+    if (rc != FX_OK) return rc;
+    snprintf(buf, (size_t)n, "fxk::sforms_kernel<%d,%d> %s P=%d budget=%d", sd, order, p.image ? "image" : "stream", p.P, p.budget);
+    return FX_OK;
+}
+
+int fx_sforms_tabulate_batch(fx_ctx* ctx, const fx_sforms_element* el, const double* lo, const double* hi, int order,
+                             int64_t nreq, int npts, const double* pts, double* out, void* stream) {
+    const char* who = "fx_sforms_tabulate_batch";
+    if (!ctx || !el || !lo || !hi) return fail(FX_EINVAL, "%s: null context, element or box", who);
+    if (nreq < 0) return fail(FX_EINVAL, "%s: negative order or count", who);
+    SfPlan p;
+    const int rc = make_plan(who, el->sd, el->degree, el->nrows, order, npts, &p);
+    if (rc != FX_OK) return rc;
+    for (int d = 0; d < el->sd; ++d)
+        if (!(hi[d] != lo[d])) return fail(FX_EINVAL, "%s: empty box in direction %d", who, d);
+    if (nreq == 0 || npts == 0) return FX_OK;
+    if (!pts || !out) return fail(FX_EINVAL, "%s: null device pointer", who);
+
+    int device = 0, num_cu = 0, lds_per_cu = 0;
+    fx::ctx_facts(ctx, &device, &num_cu, &lds_per_cu);
+    if (device != el->device) return fail(FX_EINVAL, "%s: the element lives on device %d, the context on %d", who, el->device, device);
+    if ((long long)p.lds > (long long)lds_per_cu) return fail(FX_ENOTIMPL, "%s: %zu bytes of LDS", who, p.lds);
+    fxk::SfArgs a;
+    memset(&a, 0, sizeof a);
+    a.pts = pts;
+    a.out = out;
+    a.coef = el->coef;
+    a.codes = el->codes;
+    for (int d = 0; d < 3; ++d) {
+        a.v0[d] = d < el->sd ? lo[d] : 0.0;
+        a.v1[d] = d < el->sd ? hi[d] : 1.0;
+    }
+    a.nreq = nreq;
+    a.npts = npts;
+    a.nrows = el->nrows;
+    a.ntab = p.ntab;
+    a.P = p.P;
+    a.image = p.image;
+    a.degree = el->degree;
+    a.nitems = (nreq + p.P - 1) / p.P;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
+    SF_HIP_TRY(hipSetDevice(device));
+    SF_HIP_TRY(el->sd == 2 ? launch_order<2>(order, grid, p.lds, (hipStream_t)stream, a) : launch_order<3>(order, grid, p.lds, (hipStream_t)stream, a));
+    return FX_OK;
+}
+
+}  // extern "C"

@@ -662,3 +662,64 @@ def serendipity_tabulate_batch(sd, degree, lo, hi, order, pts, out=None, stream=
     _lib.ser_check(_lib.serlib.fx_serendipity_tabulate_batch(ctx.handle, int(sd), int(degree), host_ptr(lo), host_ptr(hi), int(order),
                                                     nreq, npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
     return out
+
+
+class SFormsTable:
+    """Device-resident term table of a BDMCE / BDMCF / trimmed serendipity element (fx_sforms_element): coef (nrows, sd),
+    codes (nrows, sd, sd), see fiat_amd/sforms.py."""
+
+    def __init__(self, sd, degree, coef, codes, ctx=None):
+        self.ctx = ctx or Context.get()
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if coef.ndim != 2 or coef.shape[1] != sd or codes.shape != coef.shape + (sd,):
+            raise ValueError("coef must have shape (nrows, sd) and codes (nrows, sd, sd)")
+        self.sd, self.degree, self.nrows = int(sd), int(degree), int(coef.shape[0])
+        h = c_void_p()
+        _lib.ser_check(_lib.sflib.fx_sforms_element_create(self.ctx.handle, self.sd, self.degree, self.nrows, host_ptr(coef),
+                                                          host_ptr(codes), ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                _lib.sflib.fx_sforms_element_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+def sforms_kernel(sd, degree, nrows, order, npts):
+    """Kernel instance, output route, requests per item and image budget of a shape (fx_sforms_kernel; host only):
+    ``"fxk::sforms_kernel<sd,order> image|stream P=<p> budget=<bytes>"``."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.sflib.fx_sforms_kernel(int(sd), int(degree), int(nrows), int(order), int(npts), buf, len(buf)))
+    return buf.value.decode()
+
+
+def sforms_tabulate_batch(table, lo, hi, order, pts, out=None, stream=None):
+    """The element of ``table`` (SFormsTable) on the box [lo, hi] (fx_sforms_tabulate_batch): pts (nreq, npts, sd) ->
+    (nreq, ntab, nrows, sd, npts) on the device.  Shapes beyond the kernel raise NotImplementedError; there is no other
+    route."""
+    ctx, sd = table.ctx, table.sd
+    pts = _as_device(pts, ctx)
+    if pts.dim() != 3 or pts.shape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1)
+    if lo.shape != (sd,) or hi.shape != (sd,):
+        raise ValueError("the box needs one lower and one upper coordinate per direction")
+    if order < 0:
+        raise ValueError("negative derivative order")
+    shape = (nreq, num_tables(sd, order), table.nrows, sd, npts)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        sforms_kernel(sd, table.degree, table.nrows, order, npts)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.sflib.fx_sforms_tabulate_batch(ctx.handle, table.handle, host_ptr(lo), host_ptr(hi), int(order), nreq, npts,
+                                                      _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    return out
