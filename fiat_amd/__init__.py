@@ -43,6 +43,7 @@ from .brezzi_douglas_marini_cube import BrezziDouglasMariniCubeEdge, BrezziDougl
 from .Sminus import TrimmedSerendipityEdge, TrimmedSerendipityFace  # noqa: F401
 from .SminusCurl import TrimmedSerendipityCurl  # noqa: F401
 from .SminusDiv import TrimmedSerendipityDiv  # noqa: F401
+from .discontinuous_pc import DPC  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
@@ -70,6 +71,7 @@ supported_elements = {
     "SminusF": TrimmedSerendipityFace,
     "SminusCurl": TrimmedSerendipityCurl,
     "SminusDiv": TrimmedSerendipityDiv,
+    "DPC": DPC,
 }
 
 # (FIAT/__init__.py:130-131)

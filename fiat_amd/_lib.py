@@ -187,6 +187,31 @@ for _name, (_res, _args) in _SF_SIGS.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# The closed-form kernel of DPC is a third companion library (include/fiat_amd_dpc.h), loaded and bound like the other two.
+# No fallback: a missing companion fails the import.
+DPC_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_dpc.so")
+if not os.path.exists(DPC_LIB_PATH):
+    raise ImportError(
+        f"{DPC_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+
+dpclib = ctypes.CDLL(DPC_LIB_PATH)
+
+_DPC_SIGS = {
+    "fx_dpc_abi_version": (c_int, []),
+    "fx_dpc_descriptor": (c_int, [c_int, c_int, c_void_p]),
+    "fx_dpc_kernel": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_dpc_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
+}
+
+DPC_EXPORTS = tuple(_DPC_SIGS)
+
+for _name, (_res, _args) in _DPC_SIGS.items():
+    _fn = getattr(dpclib, _name)       # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 
 def check(rc, errlib=None):
     """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the

@@ -664,6 +664,49 @@ def serendipity_tabulate_batch(sd, degree, lo, hi, order, pts, out=None, stream=
     return out
 
 
+def dpc_descriptor(sd, degree):
+    """The dof table of DPC_degree the kernels are compiled from (fx_dpc_descriptor; host only): rows alpha, sd + 1 entries of
+    sum ``degree``, in the order of the reference's nodes."""
+    rows = np.zeros((math.comb(int(degree) + int(sd), int(sd)), sd + 1), dtype=np.int32)
+    _lib.ser_check(_lib.dpclib.fx_dpc_descriptor(int(sd), int(degree), host_ptr(rows)))
+    return rows
+
+
+def dpc_kernel(sd, degree, order, npts):
+    """Kernel instance, output route and requests per item of a shape (fx_dpc_kernel; host only):
+    ``"fxk::dpc_kernel<sd,degree,order> image|stream P=<p>"``."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.dpclib.fx_dpc_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
+    return buf.value.decode()
+
+
+def dpc_tabulate_batch(sd, degree, lam0, G, order, pts, out=None, stream=None, ctx=None):
+    """DPC_degree in closed form (fx_dpc_tabulate_batch): lambda = lam0 + G x are the barycentric coordinates of the mapped
+    simplex; pts (nreq, npts, sd) -> (nreq, ntab, ndof, npts) on the device.  Shapes beyond the compile-time instances raise
+    NotImplementedError (the element routes them to the general kernels before it gets here)."""
+    ctx = ctx or Context.get()
+    pts = _as_device(pts, ctx)
+    if pts.dim() != 3 or pts.shape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    lam0 = np.ascontiguousarray(lam0, dtype=np.float64).reshape(-1)
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    if lam0.shape != (sd + 1,) or G.shape != (sd + 1, sd):
+        raise ValueError("the barycentric map needs lam0 (sd + 1,) and G (sd + 1, sd)")
+    if order < 0:
+        raise ValueError("negative derivative order")
+    shape = (nreq, num_tables(sd, order), math.comb(int(degree) + sd, sd), npts)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        dpc_kernel(sd, degree, order, npts)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.dpclib.fx_dpc_tabulate_batch(ctx.handle, int(sd), int(degree), host_ptr(lam0), host_ptr(G), int(order), nreq,
+                                                    npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    return out
+
+
 class SFormsTable:
     """Device-resident term table of a BDMCE / BDMCF / trimmed serendipity element (fx_sforms_element): coef (nrows, sd),
     codes (nrows, sd, sd), see fiat_amd/sforms.py."""
