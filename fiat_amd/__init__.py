@@ -44,6 +44,8 @@ from .Sminus import TrimmedSerendipityEdge, TrimmedSerendipityFace  # noqa: F401
 from .SminusCurl import TrimmedSerendipityCurl  # noqa: F401
 from .SminusDiv import TrimmedSerendipityDiv  # noqa: F401
 from .discontinuous_pc import DPC  # noqa: F401
+from .hierarchical import Legendre  # noqa: F401
+from .hdiv_trace import HDivTrace  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
@@ -72,6 +74,8 @@ supported_elements = {
     "SminusCurl": TrimmedSerendipityCurl,
     "SminusDiv": TrimmedSerendipityDiv,
     "DPC": DPC,
+    "Legendre": Legendre,
+    "HDiv Trace": HDivTrace,
 }
 
 # (FIAT/__init__.py:130-131)

@@ -212,6 +212,30 @@ for _name, (_res, _args) in _DPC_SIGS.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# The fused facet kernel of the H(div) trace element is a fourth companion library (include/fiat_amd_trace.h), loaded and
+# bound like the other three.  No fallback: a missing companion fails the import.
+TRACE_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_trace.so")
+if not os.path.exists(TRACE_LIB_PATH):
+    raise ImportError(
+        f"{TRACE_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+
+tracelib = ctypes.CDLL(TRACE_LIB_PATH)
+
+_TRACE_SIGS = {
+    "fx_trace_abi_version": (c_int, []),
+    "fx_trace_kernel": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_trace_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
+TRACE_EXPORTS = tuple(_TRACE_SIGS)
+
+for _name, (_res, _args) in _TRACE_SIGS.items():
+    _fn = getattr(tracelib, _name)     # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 
 def check(rc, errlib=None):
     """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the

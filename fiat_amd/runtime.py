@@ -707,6 +707,56 @@ def dpc_tabulate_batch(sd, degree, lam0, G, order, pts, out=None, stream=None, c
     return out
 
 
+TRACE_MODES = {"identify": 0, "facet": 1, "facets": 2}      # include/fiat_amd_trace.h FX_TRACE_*
+
+
+def trace_kernel(fd, degree, nfac, npts):
+    """Kernel instance, output route and requests per item of a shape (fx_trace_kernel; host only):
+    ``"fxk::trace_kernel<fd,degree> image|stream P=<p>"``, degree -1 for the run-time-degree instance."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.tracelib.fx_trace_kernel(int(fd), int(degree), int(nfac), int(npts), buf, len(buf)))
+    return buf.value.decode()
+
+
+def trace_tabulate_batch(fd, degree, nfac, C, mode, pts, facet=0, facets=None, lam0=None, G=None, out=None, stream=None,
+                         ctx=None):
+    """The H(div) trace table in one pass (fx_trace_tabulate_batch): ``C`` (nf, nf), a device tensor, is the facet element over
+    the kernel's expansion; pts (nreq, npts, fd + 1) in cell coordinates (mode "identify", with the barycentric map lam0, G of
+    the cell) or (nreq, npts, fd) in facet coordinates (mode "facet" with ``facet``, mode "facets" with the int32 device
+    tensor ``facets`` (nreq,), which the caller has checked) -> (nreq, 1, nfac * nf, npts) on the device."""
+    ctx = ctx or Context.get()
+    pts = _as_device(pts, ctx)
+    pd = fd + 1 if mode == "identify" else fd
+    if pts.dim() != 3 or pts.shape[2] != pd:
+        raise ValueError(f"points must have shape (nreq, npts, {pd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    nf = (1, int(degree) + 1, (int(degree) + 1) * (int(degree) + 2) // 2)[fd]
+    if tuple(C.shape) != (nf, nf) or C.dtype != torch.float64 or not C.is_contiguous() or C.device != ctx.device:
+        raise ValueError("the facet element's matrix must be a contiguous float64 device tensor (nf, nf)")
+    if mode == "facets":
+        if (facets is None or tuple(facets.shape) != (nreq,) or facets.dtype != torch.int32 or not facets.is_contiguous()
+                or facets.device != ctx.device):
+            raise ValueError("facets must be a contiguous int32 device tensor (nreq,)")
+    if mode == "identify":
+        lam0 = np.ascontiguousarray(lam0, dtype=np.float64).reshape(-1)
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if lam0.shape != (fd + 2,) or G.shape != (fd + 2, fd + 1):
+            raise ValueError("the barycentric map needs lam0 (sd + 1,) and G (sd + 1, sd)")
+    shape = (nreq, 1, nfac * nf, npts)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        trace_kernel(fd, degree, nfac, npts)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.tracelib.fx_trace_tabulate_batch(
+        ctx.handle, int(fd), int(degree), int(nfac), TRACE_MODES[mode], int(facet),
+        _dev_ptr(facets) if mode == "facets" else None, _dev_ptr(C),
+        host_ptr(lam0) if mode == "identify" else None, host_ptr(G) if mode == "identify" else None,
+        nreq, npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    return out
+
+
 class SFormsTable:
     """Device-resident term table of a BDMCE / BDMCF / trimmed serendipity element (fx_sforms_element): coef (nrows, sd),
     codes (nrows, sd, sd), see fiat_amd/sforms.py."""

@@ -82,7 +82,7 @@ sys.modules["FIAT"] = _Shim("FIAT", fiat_amd)
 for sub in ("reference_element", "quadrature", "quadrature_schemes", "expansions", "polynomial_set", "functional", "dual_set", "finite_element",
             "tensor_product", "macro", "barycentric_interpolation", "jacobi", "lagrange", "discontinuous_lagrange", "nedelec", "raviart_thomas",
             "check_format_variant", "hdivcurl", "enriched", "restricted", "bubble", "orientation_utils", "pointwise_dual", "hierarchical",
-            "discontinuous_pc", "P0", "regge", "hellan_herrmann_johnson"):
+            "discontinuous_pc", "P0", "regge", "hellan_herrmann_johnson", "hdiv_trace"):
     try:
         target = importlib.import_module("fiat_amd." + sub)
     except Exception:
