@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <numeric>
 #include <vector>
 
@@ -30,6 +31,7 @@
 #include "tensor_small.hpp"
 #include "prism_small.hpp"
 #include "wg_launch.hpp"
+#include "counter_handout.hpp"
 
 namespace {
 
@@ -157,11 +159,55 @@ struct fx_ctx {
     int lds_per_cu = 0;
     std::string name;
     double* d_trash = nullptr;  // 64 KB scratch (ablation builds: wave lifetimes, FX_DBG & 512)
-    unsigned long long* d_queue = nullptr;  // chunk counters of the dynamically scheduled kernels (work_queue.hpp)
-    unsigned int launch_seq = 0;
+    // chunk counters of the dynamically scheduled kernels (work_queue.hpp), 128 B apart, in blocks of CounterHandout::BLOCK
+    // that are added as streams and captures appear and live as long as the context (counter_handout.hpp)
+    std::vector<unsigned long long*> queue_blocks;
+    fx::CounterHandout counters;
     unsigned policy = 0;      // FX_POLICY_* bits (fx_ctx_set_policy)
 };
-constexpr int FX_QUEUE_SLOTS = 64;  // counters handed to consecutive launches round-robin (128 B apart)
+
+namespace {
+bool grow_counters(fx_ctx* ctx, int first, int count) {
+    if (first != (int)ctx->queue_blocks.size() * fx::CounterHandout::BLOCK || count != fx::CounterHandout::BLOCK) return false;
+    unsigned long long* p = nullptr;
+    if (hipMalloc(&p, (size_t)count * 128) != hipSuccess || hipMemset(p, 0, (size_t)count * 128) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        return false;
+    }
+    ctx->queue_blocks.push_back(p);
+    return true;
+}
+
+// The work counter of one launch of a dynamically scheduled kernel on stream `s`: the stream's own, or -- while the stream
+// captures into a graph -- one that no direct launch ever receives (counter_handout.hpp).  After a stream's first launch this
+// is two queries of the runtime and a table look-up: no allocation, no synchronisation.
+unsigned int* work_counter(fx_ctx* ctx, hipStream_t s) {
+    unsigned long long capture = 0;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamGetCaptureInfo(s, &st, &capture) != hipSuccess) {  // (a legacy default stream beside a capture: not capturing itself)
+        (void)hipGetLastError();
+        st = hipStreamCaptureStatusNone;
+    }
+    if (st != hipStreamCaptureStatusActive) capture = 0;
+    else if (capture == 0) capture = ~0ULL;
+    // the stream's key: its handle (include/fiat_amd.h: a handle names one stream while the context lives).  hipStreamPerThread is
+    // one handle for a different stream in every thread: the thread's identity is folded in, above the address bits.
+    unsigned long long sid = (unsigned long long)reinterpret_cast<uintptr_t>(s);
+    if (s == hipStreamPerThread) sid |= (unsigned long long)(std::hash<std::thread::id>()(std::this_thread::get_id()) | 1u) << 48;
+    const int idx = ctx->counters.acquire(sid, capture, [ctx](int first, int count) { return grow_counters(ctx, first, count); });
+    if (idx == fx::CounterHandout::NO_SPARE) {
+        fail(FX_ENOMEM, "no work counter left for a captured launch (nothing may be allocated during a capture): "
+                        "make one direct call on this context before capturing");
+        return nullptr;
+    }
+    if (idx < 0) {
+        fail(FX_ENOMEM, "out of device memory for the work counters of a new stream");
+        return nullptr;
+    }
+    return reinterpret_cast<unsigned int*>(ctx->queue_blocks[idx / fx::CounterHandout::BLOCK] + (size_t)(idx % fx::CounterHandout::BLOCK) * 16);
+}
+}  // namespace
 
 // for the entry points of the other translation units (bernstein.hip): fx_last_error's message, the context's device facts
 namespace fx {
@@ -253,8 +299,8 @@ int fx_ctx_create(int device_id, fx_ctx** out) {
 #else
     const size_t trash_bytes = 64 * 1024;
 #endif
-    if (hipMalloc(&c->d_trash, trash_bytes) != hipSuccess || hipMalloc(&c->d_queue, FX_QUEUE_SLOTS * 128) != hipSuccess ||
-        hipMemset(c->d_queue, 0, FX_QUEUE_SLOTS * 128) != hipSuccess) {
+    if (hipMalloc(&c->d_trash, trash_bytes) != hipSuccess ||
+        !c->counters.reserve([c](int first, int count) { return grow_counters(c, first, count); })) {
         if (c->d_trash) (void)hipFree(c->d_trash);
         delete c;
         return fail(FX_ENOMEM, "fx_ctx_create: out of device memory");
@@ -265,7 +311,8 @@ int fx_ctx_create(int device_id, fx_ctx** out) {
 
 int fx_ctx_destroy(fx_ctx* ctx) {
     if (ctx && ctx->d_trash) (void)hipFree(ctx->d_trash);
-    if (ctx && ctx->d_queue) (void)hipFree(ctx->d_queue);
+    if (ctx)
+        for (unsigned long long* p : ctx->queue_blocks) (void)hipFree(p);
     delete ctx;
     return FX_OK;
 }
@@ -591,7 +638,7 @@ struct Launch {
     bool kodd = false;  // stacked kernel: requests of an odd number of doubles (8-byte flush instance)
     int kpiola = 0;     // stacked kernel: Piola map applied to the accumulators (PIO instance), FX_MAP_*
     double* trash = nullptr;
-    unsigned long long* queue = nullptr;
+    fx_ctx* ctx = nullptr;   // for the work counter of the dynamically scheduled kernels (work_counter, at the launch)
     // 0: LDS-image kernel (simplex_fixed.hpp), 1: K-streamed kernel (simplex_stream.hpp),
     // 2: K-streamed, two requests per wave (simplex_pair.hpp)
     int fkind = 0;
@@ -787,7 +834,9 @@ int launch_fixed(const Launch& L, hipStream_t s) {
 #endif
         static const bool verbose = ab_env("FIAT_AMD_VERBOSE") != nullptr;
         if (verbose) fprintf(stderr, "[fiat_amd] pair kernel: occupancy %d WG/CU, grid %d, lds %d B\n", occ, grid, lds_bytes);
-        hipLaunchKernelGGL(kp, dim3(grid), dim3(64 * PAIR_NW), lds_bytes, s, fa, L.trash, reinterpret_cast<unsigned int*>(L.queue));
+        unsigned int* const counter = work_counter(L.ctx, s);
+        if (!counter) return FX_ENOMEM;
+        hipLaunchKernelGGL(kp, dim3(grid), dim3(64 * PAIR_NW), lds_bytes, s, fa, L.trash, counter);
         HIP_TRY(hipGetLastError());
 #if defined(FX_DBG) && (FX_DBG & 512)
         if (verbose) HIP_TRY(report_wave_lifetimes(L.trash, grid, PAIR_NW));
@@ -990,8 +1039,9 @@ int launch_stacked(const Launch& L, hipStream_t s) {
     }
     const long long groups = CHUNK ? L.khead.nreq * ((L.khead.npts + 16 * CT - 1) / (16 * CT)) : (L.khead.nreq + G - 1) / G;
     const int grid = (int)std::max<long long>(1, std::min<long long>((groups + STACKED_NW - 1) / STACKED_NW, (long long)L.ncu * occ));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * STACKED_NW), L.klds_bytes, s, ka, L.trash,
-                       reinterpret_cast<unsigned int*>(L.queue));
+    unsigned int* const counter = work_counter(L.ctx, s);
+    if (!counter) return FX_ENOMEM;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * STACKED_NW), L.klds_bytes, s, ka, L.trash, counter);
     HIP_TRY(hipGetLastError());
 #if defined(FX_DBG) && (FX_DBG & 512)
     if (ab_env("FIAT_AMD_VERBOSE")) HIP_TRY(report_wave_lifetimes(L.trash, grid, STACKED_NW));
@@ -1021,8 +1071,7 @@ int launch_stacked(const Launch& L, hipStream_t s) {
 int launch_wg(const Launch& L, hipStream_t s) {
     const StackedShape& k = kStackedShapes[L.stacked_id];
     const int ct = L.wg_ct;
-    hipError_t e = fxwg::launch_simplex_wg(k.sd, k.n, ct, L.kodd, L.wg_mix, L.khead, L.fcoef.data(), (int)L.fcoef.size(), L.klds_bytes, L.kgrid, L.trash,
-                                           reinterpret_cast<unsigned int*>(L.queue), s);
+    hipError_t e = fxwg::launch_simplex_wg(k.sd, k.n, ct, L.kodd, L.wg_mix, L.khead, L.fcoef.data(), (int)L.fcoef.size(), L.klds_bytes, L.kgrid, L.trash, s);
     if (e != hipSuccess) return fail(FX_EHIP, "tabulate_simplex_wg<%d,%d,%d>: %s", k.sd, k.n, ct, hipGetErrorString(e));
     if (L.wg_mix) return FX_OK;   // (the chain rule has been applied)
     switch (k.sd) {
@@ -1598,9 +1647,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
             if (kk && !strcmp(kk, "pair") && pair_ok) L.fkind = 2;
             L.ncu = ctx->num_cu;
             L.trash = ctx->d_trash;
-            // the kernel leaves its counter zeroed; launches in flight at the same time (other
-            // streams) get different counters
-            L.queue = ctx->d_queue + (size_t)(ctx->launch_seq++ % FX_QUEUE_SLOTS) * 16;
+            L.ctx = ctx;   // (the paired kernel draws its work counter at the launch, when the stream is known: work_counter)
             fa.afrag = L.fkind >= 1 ? e->d_afrag_stream : e->d_afrag_split;
             fa.phi0 = e->prog.phi0;
             memcpy(fa.A0, e->A0, sizeof fa.A0);
@@ -2059,7 +2106,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                 L.kgrid = (int)std::max<long long>(1, std::min<long long>((groups + STACKED_NW - 1) / STACKED_NW, (long long)ctx->num_cu * wgs));
                 L.ncu = ctx->num_cu;
                 L.trash = ctx->d_trash;
-                L.queue = ctx->d_queue + (size_t)(ctx->launch_seq++ % FX_QUEUE_SLOTS) * 16;
+                L.ctx = ctx;
                 L.kmix_order = order;
                 L.kodd = wgk ? wg_odd : ((k.rtc == 0 && !even) || mix_odd);
                 L.kpiola = pio ? mapping : 0;
@@ -2562,13 +2609,19 @@ namespace {
 // after a synchronisation point: did a dynamically scheduled kernel give up waiting for a chunk id
 // (work_queue.hpp)?  Its output is then incomplete.
 int check_work_queues(fx_ctx* ctx) {
-    unsigned int flags[FX_QUEUE_SLOTS * 32];
-    HIP_TRY(hipMemcpy(flags, ctx->d_queue, sizeof flags, hipMemcpyDeviceToHost));
-    for (int i = 0; i < FX_QUEUE_SLOTS; ++i)
-        if (flags[i * 32 + 2]) {
-            (void)hipMemset(ctx->d_queue, 0, FX_QUEUE_SLOTS * 128);
-            return fail(FX_EHIP, "work queue protocol error in a tabulation kernel: the output is incomplete");
-        }
+    constexpr int N = fx::CounterHandout::BLOCK;
+    unsigned int flags[N * 32];
+    bool bad = false;
+    for (unsigned long long* block : ctx->queue_blocks) {
+        HIP_TRY(hipMemcpy(flags, block, sizeof flags, hipMemcpyDeviceToHost));
+        for (int i = 0; i < N; ++i)
+            if (flags[i * 32 + 2]) {
+                (void)hipMemset(block, 0, N * 128);
+                bad = true;
+                break;
+            }
+    }
+    if (bad) return fail(FX_EHIP, "work queue protocol error in a tabulation kernel: the output is incomplete");
     return FX_OK;
 }
 }  // namespace

@@ -167,8 +167,7 @@ template <int SD, int N, int NSUB, int SUB> struct SubsetSteps {
 //         tetrahedra at 74 points 320 -> 298 us; the 8-byte twins spill in the sweep at 256 registers, 394 -> 850 us, and stay
 //         at one workgroup a CU)
 template <int SD, int N, int CT, bool ODD, int PC, int MIX = 0, bool FAST = false>
-__global__ __launch_bounds__(64 * WG_NW, FAST && !ODD ? 2 : 1) void tabulate_simplex_wg(const StackedArgs<FixedNC<SD, N>::value> a, double* __restrict__ trash,
-                                                                   unsigned int* __restrict__ gctr) {
+__global__ __launch_bounds__(64 * WG_NW, FAST && !ODD ? 2 : 1) void tabulate_simplex_wg(const StackedArgs<FixedNC<SD, N>::value> a, double* __restrict__ trash) {
     constexpr StepTable<SD, N> TBL{};
     constexpr int NEXP = StepTable<SD, N>::NEXP;
     constexpr int KS = (NEXP + 3) / 4;

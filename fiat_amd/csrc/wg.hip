@@ -14,8 +14,7 @@ namespace {
 constexpr int wg_pc(int ct) { return ct % 2 == 0 ? 2 : 1; }
 
 template <int SD, int N, int CT, bool ODD, int PC, int MIX, bool FAST = false>
-hipError_t launch(const fxk::StackedArgs<0>& h, const double* coef, int ncoef, int lds_bytes, int grid, double* trash, unsigned int* queue,
-                  hipStream_t s) {
+hipError_t launch(const fxk::StackedArgs<0>& h, const double* coef, int ncoef, int lds_bytes, int grid, double* trash, hipStream_t s) {
     constexpr int NC = fxk::FixedNC<SD, N>::value;
     constexpr int KS = (fxk::StepTable<SD, N>::NEXP + 3) / 4;
     if (ncoef != NC || lds_bytes != fxk::wg_lds_doubles(CT, KS) * 8 || h.npts < 1 || h.gslab < 1 || (long long)h.gslab * h.npts > 16 * CT ||
@@ -48,18 +47,11 @@ hipError_t launch(const fxk::StackedArgs<0>& h, const double* coef, int ncoef, i
         if (e != hipSuccess) return e;
         attr = true;
     }
-#if FX_WG_DBG == 3
-    {   // is the counter slot clean when the launch takes it?
-        unsigned int q4[4];
-        if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(q4, queue, sizeof q4, hipMemcpyDeviceToHost) == hipSuccess && (q4[0] | q4[1] | q4[2] | q4[3]))
-            fprintf(stderr, "[fiat_amd] WG DIRTY SLOT %p: %u %u %u %u (nreq %lld grid %d)\n", (void*)queue, q4[0], q4[1], q4[2], q4[3], (long long)h.nreq, grid);
-    }
-#endif
 #if FX_WG_DBG
     static int dbg_launches = 0;
     if (dbg_launches++ == 0) (void)hipMemsetAsync(trash + 4096, 0, 24 * sizeof(double), s);
 #endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * fxk::WG_NW), lds_bytes, s, ka, trash, queue);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * fxk::WG_NW), lds_bytes, s, ka, trash);
 #if FX_WG_DBG
     if (FX_WG_DBG == 1 || dbg_launches % 16 == 0) {   // range-check build: report accesses that left their buffers (redirected to the scratch area by the kernel); 2: every 16th launch only (launches stay back to back)
         double rep[24];
@@ -98,35 +90,35 @@ constexpr bool wg_has_mix(int sd, int n, int ct) { return sd == 3 ? (ct == 4 || 
 
 template <int SD, int N, int CT>
 hipError_t launch_odd(bool odd, int mix, const fxk::StackedArgs<0>& h, const double* coef, int ncoef, int lds_bytes, int grid, double* trash,
-                      unsigned int* queue, hipStream_t s) {
+                      hipStream_t s) {
     if (mix) {
         if constexpr (wg_has_mix(SD, N, CT)) {
-            if (!odd) return launch<SD, N, CT, false, wg_mix_pc(SD, CT, false), 1>(h, coef, ncoef, lds_bytes, grid, trash, queue, s);
+            if (!odd) return launch<SD, N, CT, false, wg_mix_pc(SD, CT, false), 1>(h, coef, ncoef, lds_bytes, grid, trash, s);
             // (degree-6 tetrahedra on eight column tiles: the 8-byte twin spills 96 registers -- not instantiated; scalar elements of
             // that degree have 84 rows a table, their requests are never odd)
             if constexpr (!(SD == 3 && N == 6 && CT == 8))
-                return launch<SD, N, CT, true, wg_mix_pc(SD, CT, true), 1>(h, coef, ncoef, lds_bytes, grid, trash, queue, s);
+                return launch<SD, N, CT, true, wg_mix_pc(SD, CT, true), 1>(h, coef, ncoef, lds_bytes, grid, trash, s);
         }
         return hipErrorInvalidValue;
     }
     if constexpr (wg_pc(CT) == 1) {   // at most one row tile per wave (values-only requests of up to 64 rows): the FAST instances
         if (h.RT <= fxk::WG_NW)
-            return odd ? launch<SD, N, CT, true, 1, 0, true>(h, coef, ncoef, lds_bytes, grid, trash, queue, s)
-                       : launch<SD, N, CT, false, 1, 0, true>(h, coef, ncoef, lds_bytes, grid, trash, queue, s);
+            return odd ? launch<SD, N, CT, true, 1, 0, true>(h, coef, ncoef, lds_bytes, grid, trash, s)
+                       : launch<SD, N, CT, false, 1, 0, true>(h, coef, ncoef, lds_bytes, grid, trash, s);
     }
-    return odd ? launch<SD, N, CT, true, wg_pc(CT), 0>(h, coef, ncoef, lds_bytes, grid, trash, queue, s)
-               : launch<SD, N, CT, false, wg_pc(CT), 0>(h, coef, ncoef, lds_bytes, grid, trash, queue, s);
+    return odd ? launch<SD, N, CT, true, wg_pc(CT), 0>(h, coef, ncoef, lds_bytes, grid, trash, s)
+               : launch<SD, N, CT, false, wg_pc(CT), 0>(h, coef, ncoef, lds_bytes, grid, trash, s);
 }
 
 template <int SD, int N>
 hipError_t launch_ct(int ct, bool odd, int mix, const fxk::StackedArgs<0>& h, const double* coef, int ncoef, int lds_bytes, int grid, double* trash,
-                     unsigned int* queue, hipStream_t s) {
+                     hipStream_t s) {
     constexpr int KS = (fxk::StepTable<SD, N>::NEXP + 3) / 4;
     switch (ct) {
-        case 4: return launch_odd<SD, N, 4>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, queue, s);
-        case 5: return launch_odd<SD, N, 5>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, queue, s);
-        case 6: return launch_odd<SD, N, 6>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, queue, s);
-        case 8: if constexpr (fxk::wg_lds_doubles(8, KS) * 8 <= 160 * 1024) return launch_odd<SD, N, 8>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, queue, s); break;
+        case 4: return launch_odd<SD, N, 4>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, s);
+        case 5: return launch_odd<SD, N, 5>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, s);
+        case 6: return launch_odd<SD, N, 6>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, s);
+        case 8: if constexpr (fxk::wg_lds_doubles(8, KS) * 8 <= 160 * 1024) return launch_odd<SD, N, 8>(odd, mix, h, coef, ncoef, lds_bytes, grid, trash, s); break;
     }
     return hipErrorInvalidValue;
 }
@@ -163,14 +155,14 @@ int mix_ct(int sd, int n, int ctn) {
 }
 
 hipError_t launch_simplex_wg(int sd, int n, int ct, bool odd, int mix, const fxk::StackedArgs<0>& h, const double* coef, int ncoef, int lds, int grid,
-                             double* trash, unsigned int* queue, hipStream_t s) {
+                             double* trash, hipStream_t s) {
     if (!has_instance(sd, n, ct, odd) || (mix && !has_mix_instance(sd, n, ct, odd))) return hipErrorInvalidValue;
-    if (sd == 3 && n == 6) return launch_ct<3, 6>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
-    if (sd == 3 && n == 5) return launch_ct<3, 5>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
-    if (sd == 3 && n == 4) return launch_ct<3, 4>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
-    if (sd == 3 && n == 3) return launch_ct<3, 3>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
-    if (sd == 2 && n == 6) return launch_ct<2, 6>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
-    if (sd == 2 && n == 5) return launch_ct<2, 5>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, queue, s);
+    if (sd == 3 && n == 6) return launch_ct<3, 6>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
+    if (sd == 3 && n == 5) return launch_ct<3, 5>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
+    if (sd == 3 && n == 4) return launch_ct<3, 4>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
+    if (sd == 3 && n == 3) return launch_ct<3, 3>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
+    if (sd == 2 && n == 6) return launch_ct<2, 6>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
+    if (sd == 2 && n == 5) return launch_ct<2, 5>(ct, odd, mix, h, coef, ncoef, lds, grid, trash, s);
     return hipErrorInvalidValue;
 }
 

@@ -16,8 +16,7 @@ bool has_mix_instance(int sd, int n, int ct, bool odd);
 int mix_ct(int sd, int n, int ctn);
 // persistent workgroups a CU holds of the instance that takes requests of rt row tiles (2: the one-row-tile instances)
 int workgroups_per_cu(int sd, int n, int ct, bool odd, int mix, int rt);
-// one launch: `grid` persistent workgroups of 256 threads, requests handed out through queue[0] (zero before the launch,
-// zero again after it), queue[1] = finished workgroups
+// one launch: `grid` persistent workgroups of 256 threads, each with a static share of the requests (no work counter)
 hipError_t launch_simplex_wg(int sd, int n, int ct, bool odd, int mix, const fxk::StackedArgs<0>& head, const double* coef, int ncoef, int lds_bytes,
-                             int grid, double* trash, unsigned int* queue, hipStream_t s);
+                             int grid, double* trash, hipStream_t s);
 }  // namespace fxwg

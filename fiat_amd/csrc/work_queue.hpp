@@ -27,7 +27,9 @@
 //
 // The global counter cleans up after itself: the last wave of the last workgroup to finish sets
 // it back to zero (gctr[0] chunk counter, gctr[1] finished workgroups; gctr[2] = protocol-error mark), so a launch costs no
-// extra memset node; the host hands concurrent launches different counters (api.hip).
+// extra memset node.  The kernels trust the counter completely, so the host must never give it to two launches that may run
+// at the same time: every stream has its own counter, and launches captured into a graph get counters that no direct launch
+// ever receives (counter_handout.hpp; api.hip work_counter).
 //
 // LDS control block (64 bytes at the start of dynamic LDS):
 //   ctl[0]            claims of this workgroup so far (k); unit = chunk(k >> 3) * 8 + (k & 7)

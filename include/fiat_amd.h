@@ -16,6 +16,17 @@
  *     message retrievable with fx_last_error() (thread local);
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); all
  *     work is enqueued asynchronously on it, nothing synchronises unless said;
+ *   - streams: any number of streams may have work of one context pending at the
+ *     same time, directly or through captured graphs replayed on any stream.  A
+ *     stream handle is taken to name ONE stream for as long as the context lives:
+ *     destroy a stream only after its work has finished.  One instantiated graph is
+ *     in flight at most once at a time (as HIP itself arranges); a graph that holds
+ *     launches of this library is not instantiated twice to run beside itself;
+ *   - threads: a context, and the elements created on it, are driven by ONE host
+ *     thread at a time.  The launch path keeps unlocked state per context (the work
+ *     counters of its streams, tables built at first use); callers that launch from
+ *     several threads serialise their calls on a context with a lock of their own,
+ *     or give every thread its own context;
  *   - there is NO CPU fallback: with no usable gfx950 device fx_ctx_create fails.
  */
 #ifndef FIAT_AMD_H

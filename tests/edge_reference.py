@@ -429,6 +429,30 @@ def launched(call):
     return {e.name for e in prof.events() if e.device_type.name == "CUDA" and "Memcpy" not in e.name and "Memset" not in e.name}
 
 
+def launched_records(call, trace_path):
+    """The device kernels that ``call`` launches, with where and when they ran: a list of
+    ``{"name", "start", "end" (microseconds on the device's clock), "stream", "grid" (workgroups)}`` from the profiler's
+    device-side records (its trace file, written to ``trace_path``: the Python event objects carry neither stream nor grid)."""
+    import json
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        call()
+        torch.cuda.synchronize()
+    prof.export_chrome_trace(str(trace_path))
+    with open(trace_path) as f:
+        events = json.load(f)["traceEvents"]
+    out = []
+    for e in events:
+        if e.get("cat") != "kernel":
+            continue
+        args = e.get("args", {})
+        out.append({"name": e["name"], "start": float(e["ts"]), "end": float(e["ts"]) + float(e["dur"]),
+                    "stream": args.get("stream"), "grid": int(args["grid"][0])})
+    return sorted(out, key=lambda r: r["start"])
+
+
 def compare(call, shape, device):
     """call(out) for a fresh out and for guarded views at every offset."""
     import torch
