@@ -44,7 +44,7 @@ from .Sminus import TrimmedSerendipityEdge, TrimmedSerendipityFace  # noqa: F401
 from .SminusCurl import TrimmedSerendipityCurl  # noqa: F401
 from .SminusDiv import TrimmedSerendipityDiv  # noqa: F401
 from .discontinuous_pc import DPC  # noqa: F401
-from .hierarchical import Legendre  # noqa: F401
+from .hierarchical import IntegratedLegendre, Legendre  # noqa: F401
 from .hdiv_trace import HDivTrace  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
 
@@ -75,6 +75,7 @@ supported_elements = {
     "SminusDiv": TrimmedSerendipityDiv,
     "DPC": DPC,
     "Legendre": Legendre,
+    "Integrated Legendre": IntegratedLegendre,
     "HDiv Trace": HDivTrace,
 }
 

@@ -237,6 +237,32 @@ for _name, (_res, _args) in _TRACE_SIGS.items():
     _fn.argtypes = _args
 
 
+# The direct C0-hierarchy kernel of IntegratedLegendre is a fifth companion library (include/fiat_amd_hier.h), loaded and
+# bound like the other four.  No fallback: a missing companion fails the import.
+HIER_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_hier.so")
+if not os.path.exists(HIER_LIB_PATH):
+    raise ImportError(
+        f"{HIER_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+
+hierlib = ctypes.CDLL(HIER_LIB_PATH)
+
+_HIER_SIGS = {
+    "fx_hier_abi_version": (c_int, []),
+    "fx_hier_descriptor": (c_int, [c_int, c_int, c_void_p]),
+    "fx_hier_kernel": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_hier_tabulate_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+}
+
+HIER_EXPORTS = tuple(_HIER_SIGS)
+
+for _name, (_res, _args) in _HIER_SIGS.items():
+    _fn = getattr(hierlib, _name)      # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+
 def check(rc, errlib=None):
     """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the
     text; default: the main library)."""

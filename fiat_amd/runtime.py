@@ -707,6 +707,51 @@ def dpc_tabulate_batch(sd, degree, lam0, G, order, pts, out=None, stream=None, c
     return out
 
 
+def hier_descriptor(sd, degree):
+    """The dof table of IntegratedLegendre(degree) the kernels are compiled from (fx_hier_descriptor; host only): rows
+    (p, q, r, entity dimension), in the order of the reference's dofs."""
+    rows = np.zeros((math.comb(int(degree) + int(sd), int(sd)), 4), dtype=np.int32)
+    _lib.ser_check(_lib.hierlib.fx_hier_descriptor(int(sd), int(degree), host_ptr(rows)))
+    return rows
+
+
+def hier_kernel(sd, degree, order, npts):
+    """Kernel instance, output route and requests per item of a shape (fx_hier_kernel; host only):
+    ``"fxk::hier_kernel<sd,degree,order> image|stream P=<p>"``."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.hierlib.fx_hier_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
+    return buf.value.decode()
+
+
+def hier_tabulate_batch(sd, degree, order, scales, A, b, pts, out=None, stream=None, ctx=None):
+    """IntegratedLegendre(degree) from the C0 hierarchy (fx_hier_tabulate_batch): X = A x + b maps the cell onto the
+    (-1, 1)^sd simplex, ``scales`` holds one factor per entity dimension; pts (nreq, npts, sd) -> (nreq, ntab, ndof, npts) on
+    the device.  Shapes beyond the compile-time instances raise NotImplementedError (the element routes them to the general
+    kernels before it gets here)."""
+    ctx = ctx or Context.get()
+    pts = _as_device(pts, ctx)
+    if pts.dim() != 3 or pts.shape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    scales = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+    if A.shape != (sd, sd) or b.shape != (sd,) or scales.shape != (4,):
+        raise ValueError("the cell map needs A (sd, sd) and b (sd,), the scales four entries")
+    if order < 0:
+        raise ValueError("negative derivative order")
+    shape = (nreq, num_tables(sd, order), math.comb(int(degree) + sd, sd), npts)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        hier_kernel(sd, degree, order, npts)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.hierlib.fx_hier_tabulate_batch(ctx.handle, int(sd), int(degree), int(order), host_ptr(scales), _dev_ptr(pts),
+                                                      nreq, npts, _dev_ptr(out), _stream_ptr(stream), host_ptr(A), host_ptr(b)))
+    return out
+
+
 TRACE_MODES = {"identify": 0, "facet": 1, "facets": 2}      # include/fiat_amd_trace.h FX_TRACE_*
 
 
