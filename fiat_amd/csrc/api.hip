@@ -225,7 +225,9 @@ void line_facts(const fx_line_element* e, fxk::LineDesc* L);  // (below, after f
 
 #include "comm.hpp"
 
-constexpr int FX_MAX_ORDER = 8;  // highest derivative order served (orders > 2 through differentiation matrices)
+// highest derivative order served (orders > 2 through differentiation matrices): the one constant that sizes the any-order
+// table-mixing pass (table_kernels.hpp)
+constexpr int FX_MAX_ORDER = fxk::MIXA_MAX_ORDER;
 
 struct fx_element {
     fx_ctx* ctx = nullptr;
@@ -3101,7 +3103,8 @@ int mix_any_order(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int
     ma.slices = std::max(1, std::min(16, (ma.n + 1023) / 1024));
     ma.nreq = nreq;
     ma.order = order;
-    if (order > 9 || nreq * ma.slices > 0x7fffffffLL) return fail(FX_EINVAL, "batch too large for the table-mixing pass");
+    if (order > FX_MAX_ORDER) return fail(FX_ENOTIMPL, "derivative order %d > %d is not implemented by the table-mixing pass", order, FX_MAX_ORDER);
+    if (nreq * ma.slices > 0x7fffffffLL) return fail(FX_EINVAL, "batch too large for the table-mixing pass");
     std::vector<std::vector<int>> prev = fx::multi_indices(sd, 0);
     int t = 1, moff = 0;
     ma.first[0] = 0;

@@ -356,21 +356,28 @@ __global__ __launch_bounds__(256) void table_mix_high_kernel(const TableMixHighA
 // Run-time order: M_1..M_order in dynamic LDS (3-D, order 8: 4916 doubles), one workgroup per (request, slice of positions);
 // the tables of one order of a position in registers (<= 45 in 3-D).  FIAT/expansions.py:411-447 applies the chain rule through
 // Jinv at any order; this is its per-request form.
-constexpr int MIXA_MAXT = 165;   // tables up to order 8 in 3-D
+constexpr int MIXA_MAX_ORDER = 8;  // highest order of the pass: every array below is sized for it (api.hip: FX_MAX_ORDER)
+constexpr int mixa_binom(int n, int k) { return k == 0 ? 1 : mixa_binom(n - 1, k - 1) * n / k; }
+constexpr int MIXA_MAXT = mixa_binom(3 + MIXA_MAX_ORDER, 3);   // tables of orders 0..MIXA_MAX_ORDER in 3-D: 165
+// tables of exactly order MIXA_MAX_ORDER in SD dimensions: what a position keeps in registers
+template <int SD>
+constexpr int MIXA_CMAX = mixa_binom(SD - 1 + MIXA_MAX_ORDER, SD - 1);
+static_assert(MIXA_CMAX<1> == 1 && MIXA_CMAX<2> == 9 && MIXA_CMAX<3> == 45, "tables of order MIXA_MAX_ORDER: 1 / 9 / 45");
+static_assert(MIXA_CMAX<3> - 1 <= 127, "down[][] holds table indices within one order as signed char");
 struct TableMixAnyArgs {
     double* out;          // [nreq][ntab][n]   n = rows * npts
     const double* verts;  // [nreq][SD+1][SD]
     double A0inv[9];
     int n, slices, order;
     long long nreq;
-    int first[10], cnt[10], moff[10];   // per order k: first table, number of tables, offset of M_k in LDS (doubles)
+    int first[MIXA_MAX_ORDER + 1], cnt[MIXA_MAX_ORDER + 1], moff[MIXA_MAX_ORDER + 1];   // per order k: first table, number of tables, offset of M_k in LDS (doubles)
     signed char down[MIXA_MAXT][3];     // index, within the previous order, of alpha_t - e_c (-1: alpha_t[c] == 0)
     unsigned char lead[MIXA_MAXT];      // first non-zero entry of alpha_t
 };
 
 template <int SD>
 __global__ __launch_bounds__(256) void table_mix_any_kernel(const TableMixAnyArgs a) {
-    constexpr int CMAX = SD == 1 ? 1 : SD == 2 ? 9 : 45;   // tables of one order, order <= 8
+    constexpr int CMAX = MIXA_CMAX<SD>;   // tables of one order, order <= MIXA_MAX_ORDER: 1 / 9 / 45
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double* sK = sm;            // [SD * SD]
     double* sM = sm + 16;       // M_1 .. M_order
