@@ -263,6 +263,36 @@ for _name, (_res, _args) in _HIER_SIGS.items():
     _fn.argtypes = _args
 
 
+# The fused evaluation kernel (dof vectors in, values out) is a sixth companion library (include/fiat_amd_eval.h), loaded and
+# bound like the other five.  No fallback: a missing companion fails the import.
+EVAL_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_eval.so")
+if not os.path.exists(EVAL_LIB_PATH):
+    raise ImportError(
+        f"{EVAL_LIB_PATH} not found: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+
+evallib = ctypes.CDLL(EVAL_LIB_PATH)
+
+_EVAL_SIGS = {
+    "fx_eval_abi_version": (c_int, []),
+    "fx_eval_walk_order": (c_int, [c_int, c_int, c_void_p]),
+    "fx_eval_fold": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fx_eval_element_create": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int, c_int, c_void_p,
+                                       POINTER(c_void_p)]),
+    "fx_eval_element_destroy": (c_int, [c_void_p]),
+    "fx_eval_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_eval_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+}
+
+EVAL_EXPORTS = tuple(_EVAL_SIGS)
+
+for _name, (_res, _args) in _EVAL_SIGS.items():
+    _fn = getattr(evallib, _name)      # AttributeError here = ABI mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+
 def check(rc, errlib=None):
     """Map C status codes to the exception types the reference raises (``errlib``: the library whose error slot holds the
     text; default: the main library)."""

@@ -5,6 +5,8 @@ Construction assembles V = dual.to_riesz(P) . coeffs^T and solves V^T X = B on
 the device (fx_vandermonde_solve_batch); tabulate() runs the HIP tabulation
 kernel.  A singular Vandermonde matrix raises numpy.linalg.LinAlgError, as in the
 reference (:151-156)."""
+import contextlib
+
 import numpy
 
 from . import runtime
@@ -65,6 +67,15 @@ class FiniteElement:
 
     def is_macroelement(self):
         return self.ref_el is not self.ref_complex
+
+    def evaluate_batch(self, order, points, dofs, verts=None, out=None, stream=None, pushforward=False, *, route=None):
+        """``sum_i dofs[r, (j,) i] D^alpha phi_i(x_rq)`` for every request: see the module's ``evaluate_batch``."""
+        return evaluate_batch(self, order, points, dofs, verts=verts, out=out, stream=stream, pushforward=pushforward,
+                              route=route)
+
+    def evaluate_kernel(self, order, npts, nrhs=1, has_verts=False, pushforward=False):
+        """Kernel instance and route ``evaluate_batch`` takes for a request shape, as text: see ``evaluate_kernel``."""
+        return evaluate_kernel(self, order, npts, nrhs=nrhs, has_verts=has_verts, pushforward=pushforward)
 
 
 class CiarletElement(FiniteElement):
@@ -178,6 +189,158 @@ class CiarletElement(FiniteElement):
     @staticmethod
     def is_nodal():
         return True
+
+
+EVAL_KERNEL_MAXK, EVAL_KERNEL_MAXORDER, EVAL_MAXRHS = 6, 2, 8     # the instance set of csrc/evaluate.hpp
+_EVAL_MAPPINGS = ("affine", "covariant piola", "contravariant piola")
+
+
+def fused_evaluation_refusal(element, order):
+    """None where the fused evaluation kernel (csrc/evaluate.hpp) applies to ``element`` at derivative order ``order``,
+    otherwise the reason it does not, as text."""
+    if not isinstance(element, CiarletElement):
+        return f"{type(element).__name__} is not a Ciarlet element over a simplex expansion set"
+    poly_set = element.poly_set
+    es = poly_set.get_expansion_set()
+    if hasattr(es, "device_line"):
+        return "the nodal basis is the 1-D primal Lagrange basis, not a simplex polynomial set"
+    if getattr(es, "num_cells", None) != 1:
+        return "the nodal basis lives on a macro cell"
+    if poly_set.get_reference_element().get_shape() != element.ref_el.get_shape():
+        return "the element's cell is not the cell of its polynomial set"
+    sd = element.ref_el.get_spatial_dimension()
+    if sd not in (1, 2, 3):
+        return f"spatial dimension {sd}"
+    if element._expansion_variant not in (None, "bubble"):
+        return f"expansion variant {element._expansion_variant!r}"
+    degree = poly_set.get_embedded_degree()
+    if not 1 <= degree <= EVAL_KERNEL_MAXK:
+        return f"embedded degree {degree} (the kernel covers 1..{EVAL_KERNEL_MAXK})"
+    if not 0 <= order <= EVAL_KERNEL_MAXORDER:
+        return f"derivative order {order} (the kernel covers 0..{EVAL_KERNEL_MAXORDER})"
+    shape = tuple(poly_set.get_shape())
+    if shape not in ((), (sd,)):
+        return f"value shape {shape} (the kernel covers () and ({sd},))"
+    if element._mapping not in _EVAL_MAPPINGS:
+        return f"mapping {element._mapping!r}"
+    if not isinstance(element.device_polyset(), runtime.SimplexPolySet):
+        return "the nodal basis is not a SimplexPolySet on the device"
+    return None
+
+
+def _eval_element(element):
+    """The element's device form for the fused kernel (fx_eval_element), created at first use."""
+    dev = element.__dict__.get("_eval_dev")
+    if dev is None:
+        poly_set = element.poly_set
+        dev = runtime.EvalElement(element.ref_el.get_spatial_dimension(), poly_set.get_embedded_degree(),
+                                  element._expansion_variant, element._expansion_scale,
+                                  numpy.asarray(poly_set.get_reference_element().get_vertices(), dtype=float),
+                                  poly_set.get_coeffs(), value_shape=poly_set.get_shape())
+        element._eval_dev = dev
+    return dev
+
+
+def _general_tables(element, order, points, verts, pushforward, stream):
+    kwargs = {}
+    if verts is not None:
+        kwargs["verts"] = verts
+    if pushforward:
+        kwargs["pushforward"] = True
+    if stream is not None:
+        kwargs["stream"] = stream
+    return element.tabulate_batch(order, points, **kwargs)
+
+
+def evaluate_kernel(element, order, npts, nrhs=1, has_verts=False, pushforward=False):
+    """What ``evaluate_batch`` runs for a request shape: ``"fused: fxk::eval_kernel<sd,order,vdim> degree=<n> P=<requests per
+    item> chunks=<point chunks per request>"`` (fx_eval_kernel), or ``"general: tabulate_batch + einsum (<why not fused>)"``."""
+    why = fused_evaluation_refusal(element, int(order))
+    if why is None and pushforward and not has_verts:
+        raise ValueError("a push-forward needs the physical cells (verts)")
+    if why is not None:
+        return f"general: tabulate_batch + einsum ({why})"
+    poly_set = element.poly_set
+    shape = tuple(poly_set.get_shape())
+    sd = element.ref_el.get_spatial_dimension()
+    return "fused: " + runtime.eval_kernel(sd, poly_set.get_embedded_degree(), order, sd if shape else 1, len(poly_set.get_coeffs()),
+                                           npts, nrhs)
+
+
+def evaluate_batch(element, order, points, dofs, verts=None, out=None, stream=None, pushforward=False, *, route=None):
+    """Finite element functions at points, batched: points (nreq, npts, sd), dofs (nreq, ndof) or (nreq, nrhs, ndof) with
+    1 <= nrhs <= 8 (float64, host or device) -> device tensor (nreq, ntab, [nrhs,] *value_shape, npts), tables in mis() order,
+
+        out[r, t, j, ..., q] = sum_i dofs[r, j, i] * tabulate_batch(order, points, verts=verts, pushforward=pushforward)[r, t, i, ..., q].
+
+    ``verts`` and ``pushforward`` mean what they mean for ``tabulate_batch``.  ``route=None`` takes the fused kernel
+    (fx_eval_batch: the table is never formed in device memory) where it applies -- Ciarlet elements over a simplex polynomial
+    set, expansion variant default or "bubble", embedded degree 1-6, order 0-2, value shape () or (sd,), affine or single Piola
+    map -- and otherwise the general route, ``tabulate_batch`` followed by ``torch.einsum``; ``route="general"`` forces that
+    composition, ``route="fused"`` the kernel (NotImplementedError with the reason where it does not apply).  Everything is
+    validated before anything is launched (ValueError); the work is ordered on ``stream``."""
+    import torch
+    if route not in (None, "fused", "general"):
+        raise ValueError(f"unknown route {route!r}")
+    order = int(order)
+    if order < 0:
+        raise ValueError("negative derivative order")
+    sd = element.get_reference_element().get_spatial_dimension()
+    ndof = element.space_dimension()
+    pshape = tuple(points.shape) if hasattr(points, "shape") else numpy.shape(points)
+    if len(pshape) != 3 or pshape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {pshape}")
+    nreq, npts = int(pshape[0]), int(pshape[1])
+    if isinstance(dofs, torch.Tensor):
+        if dofs.dtype != torch.float64:
+            raise ValueError(f"dofs must be float64, got {dofs.dtype}")
+    else:
+        dofs = numpy.asarray(dofs)
+        if dofs.dtype != numpy.float64:
+            raise ValueError(f"dofs must be float64, got {dofs.dtype}")
+    dshape = tuple(dofs.shape)
+    if len(dshape) not in (2, 3) or dshape[0] != nreq or dshape[-1] != ndof:
+        raise ValueError(f"dofs must have shape ({nreq}, {ndof}) or ({nreq}, nrhs, {ndof}), got {dshape}")
+    squeeze = len(dshape) == 2
+    nrhs = 1 if squeeze else int(dshape[1])
+    if not 1 <= nrhs <= EVAL_MAXRHS:
+        raise ValueError(f"{nrhs} right-hand sides: evaluate_batch takes 1..{EVAL_MAXRHS} per call")
+    if verts is not None:
+        vshape = tuple(verts.shape) if hasattr(verts, "shape") else numpy.shape(verts)
+        if vshape != (nreq, sd + 1, sd):
+            raise ValueError(f"verts must have shape ({nreq}, {sd + 1}, {sd}), got {vshape}")
+    if pushforward and verts is None:
+        raise ValueError("a push-forward needs the physical cells (verts)")
+    vshape_el = tuple(element.value_shape())
+    ntab = runtime.num_tables(sd, order)
+    shape = (nreq, ntab) + (() if squeeze else (nrhs,)) + vshape_el + (npts,)
+    ctx = runtime.Context.get()
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float64
+                            or not out.is_contiguous() or out.device != ctx.device):
+        raise ValueError(f"out must be a contiguous float64 device tensor of shape {shape}")
+    vdim = int(numpy.prod(vshape_el, dtype=int)) if vshape_el else 1
+    if ntab * nrhs * vdim * npts >= 2 ** 31 or nreq * ntab * nrhs * vdim * npts >= 2 ** 62:
+        raise ValueError("the request or the batch does not fit the index arithmetic of the kernels")
+    why = fused_evaluation_refusal(element, order) if route != "general" else "route='general'"
+    if route == "fused" and why is not None:
+        raise NotImplementedError(f"the fused evaluation kernel does not apply: {why}")
+    if why is None:
+        dev = _eval_element(element)
+        d3 = runtime._as_device(dofs, ctx).reshape(nreq, nrhs, ndof)
+        o5 = None if out is None else out.view((nreq, ntab, nrhs) + vshape_el + (npts,))
+        res = runtime.eval_batch(dev, order, points, d3, verts=verts, out=o5, stream=stream,
+                                 mapping=element._mapping if pushforward else None)
+        return out if out is not None else res.view(shape)
+    # the composition a user can write: the table, then the contraction
+    with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+        tables = _general_tables(element, order, points, verts, pushforward, stream)
+        d3 = runtime._as_device(dofs, ctx).reshape(nreq, nrhs, ndof)
+        res = torch.einsum("rji,rti...->rtj...", d3, tables)
+        res = res.reshape(shape)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res.contiguous()
 
 
 def entity_support_dofs(elem, entity_dim):

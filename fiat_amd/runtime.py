@@ -752,6 +752,86 @@ def hier_tabulate_batch(sd, degree, order, scales, A, b, pts, out=None, stream=N
     return out
 
 
+class EvalElement:
+    """Device form of a polynomial set for the fused evaluation kernel (fx_eval_element): the coefficients folded over the
+    raw recurrence in the order of the kernel's walk, and the walk's step table."""
+
+    def __init__(self, sd, degree, variant, scale, cell, coeffs, value_shape=(), ctx=None):
+        self.ctx = ctx or Context.get()
+        self.sd, self.degree, self.variant = int(sd), int(degree), variant
+        self.value_shape = tuple(value_shape)
+        self.vdim = int(np.prod(self.value_shape, dtype=int)) if self.value_shape else 1
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        self.ndof = coeffs.shape[0]
+        self.nexp = math.comb(self.degree + self.sd, self.sd)
+        if coeffs.size != self.ndof * self.vdim * self.nexp:
+            raise ValueError(f"coefficients must have shape (ndof, *value_shape, {self.nexp})")
+        cell = None if cell is None else np.ascontiguousarray(cell, dtype=np.float64).reshape(self.sd + 1, self.sd)
+        h = c_void_p()
+        _lib.ser_check(_lib.evallib.fx_eval_element_create(self.ctx.handle, self.sd, self.degree, VARIANTS[variant],
+                                                          -1.0 if scale is None else float(scale),
+                                                          None if cell is None else host_ptr(cell), self.ndof, self.vdim,
+                                                          host_ptr(coeffs), ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.evallib.fx_eval_element_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def kernel(self, order, npts, nrhs=1):
+        return eval_kernel(self.sd, self.degree, order, self.vdim, self.ndof, npts, nrhs)
+
+
+def eval_kernel(sd, degree, order, vdim, ndof, npts, nrhs=1):
+    """Kernel instance and item scheme of a shape (fx_eval_kernel; host only):
+    ``"fxk::eval_kernel<sd,order,vdim> degree=<n> P=<requests per item> chunks=<point chunks per request>"``."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.ser_check(_lib.evallib.fx_eval_kernel(int(sd), int(degree), int(order), int(vdim), int(ndof), int(npts), int(nrhs), buf,
+                                              len(buf)))
+    return buf.value.decode()
+
+
+def eval_batch(elem, order, pts, dofs, verts=None, out=None, stream=None, mapping=None):
+    """sum_i dofs[r, j, i] D^alpha phi_i(x_rq) by the fused kernel (fx_eval_batch): pts (nreq, npts, sd), dofs
+    (nreq, nrhs, ndof), verts (nreq, sd + 1, sd) or None -> out (nreq, ntab, nrhs, *value_shape, npts) on the device, tables in
+    mis() order.  Everything is validated here or in the C entry before anything is launched; shapes beyond the instance set
+    raise NotImplementedError."""
+    ctx = elem.ctx
+    sd = elem.sd
+    pts = _as_device(pts, ctx)
+    dofs = _as_device(dofs, ctx)
+    if pts.dim() != 3 or pts.shape[2] != sd:
+        raise ValueError(f"points must have shape (nreq, npts, {sd}), got {tuple(pts.shape)}")
+    nreq, npts = int(pts.shape[0]), int(pts.shape[1])
+    if dofs.dim() != 3 or dofs.shape[0] != nreq or dofs.shape[2] != elem.ndof:
+        raise ValueError(f"dofs must have shape ({nreq}, nrhs, {elem.ndof}), got {tuple(dofs.shape)}")
+    nrhs = int(dofs.shape[1])
+    if verts is not None:
+        verts = _as_device(verts, ctx)
+        if tuple(verts.shape) != (nreq, sd + 1, sd):
+            raise ValueError("verts must have shape (nreq, sd+1, sd)")
+    if mapping is not None and mapping not in SimplexPolySet.MAPPINGS:
+        raise ValueError(f"unknown mapping {mapping!r}")
+    code = SimplexPolySet.MAPPINGS[mapping] if mapping else 0
+    if order < 0:
+        raise ValueError("negative derivative order")
+    shape = (nreq, num_tables(sd, order), nrhs) + elem.value_shape + (npts,)
+    if out is None:
+        # (the plan is asked first: a shape without an instance raises before anything is allocated)
+        elem.kernel(order, npts, nrhs)
+        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    _lib.ser_check(_lib.evallib.fx_eval_batch(ctx.handle, elem.handle, code, int(order), nreq, npts, nrhs, _dev_ptr(pts),
+                                             None if verts is None else _dev_ptr(verts), _dev_ptr(dofs), _dev_ptr(out),
+                                             _stream_ptr(stream)))
+    return out
+
+
 TRACE_MODES = {"identify": 0, "facet": 1, "facets": 2}      # include/fiat_amd_trace.h FX_TRACE_*
 
 
