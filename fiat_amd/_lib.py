@@ -121,18 +121,25 @@ for _name, (_res, _args) in _SIGS.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
-# The Serendipity kernels live in a companion library (include/fiat_amd_serendipity.h), built beside the default main
-# library and linked against it: it is loaded after the main one so that both share one error slot and the contexts.
-# Under a FIAT_AMD_LIB override the companion still resolves the default libfiat_amd.so of its own directory.  No
-# fallback: a missing companion fails the import.
-SER_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_serendipity.so")
-if not os.path.exists(SER_LIB_PATH):
-    raise ImportError(
-        f"{SER_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+# The later kernel families live in companion libraries (include/fiat_amd_<stem>.h), built beside the default main library
+# and linked against it: they are loaded after the main one so that all share one error slot and the contexts.  Under a
+# FIAT_AMD_LIB override a companion still resolves the default libfiat_amd.so of its own directory.  No fallback: a missing
+# companion fails the import.
+def _load_companion(stem, sigs):
+    path = os.path.join(_HERE, "csrc", f"libfiat_amd_{stem}.so")
+    if not os.path.exists(path):
+        raise ImportError(
+            f"{path} not found: build the HIP extension first "
+            "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
+    companion = ctypes.CDLL(path)
+    for name, (res, args) in sigs.items():
+        fn = getattr(companion, name)      # AttributeError here = ABI mismatch: fail loudly
+        fn.restype = res
+        fn.argtypes = args
+    return path, companion, tuple(sigs)
 
-serlib = ctypes.CDLL(SER_LIB_PATH)
 
+# Serendipity
 _SER_SIGS = {
     "fx_serendipity_abi_version": (c_int, []),
     "fx_serendipity_dims": (c_int, [c_int, c_int, _p_i]),
@@ -142,35 +149,7 @@ _SER_SIGS = {
                                               c_void_p, c_void_p]),
 }
 
-SER_EXPORTS = tuple(_SER_SIGS)
-
-for _name, (_res, _args) in _SER_SIGS.items():
-    _fn = getattr(serlib, _name)       # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# the main library the companion is linked against (its error slot): ``lib`` itself unless FIAT_AMD_LIB overrides that
-_DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd.so")
-_ser_main = lib if os.path.realpath(LIB_PATH) == os.path.realpath(_DEFAULT_LIB_PATH) else ctypes.CDLL(_DEFAULT_LIB_PATH)
-_ser_main.fx_last_error.restype = c_char_p
-_ser_main.fx_last_error.argtypes = []
-
-
-def ser_check(rc):
-    """``check`` for the companion's entries."""
-    return check(rc, _ser_main)
-
-
-# The term-table kernel of BDMCE / BDMCF and the trimmed serendipity families is a second companion library
-# (include/fiat_amd_sforms.h), loaded and bound like the first.  No fallback: a missing companion fails the import.
-SF_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_sforms.so")
-if not os.path.exists(SF_LIB_PATH):
-    raise ImportError(
-        f"{SF_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
-
-sflib = ctypes.CDLL(SF_LIB_PATH)
-
+# the term-table kernel of BDMCE / BDMCF and the trimmed serendipity families
 _SF_SIGS = {
     "fx_sforms_abi_version": (c_int, []),
     "fx_sforms_element_create": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
@@ -180,23 +159,7 @@ _SF_SIGS = {
                                          c_void_p]),
 }
 
-SF_EXPORTS = tuple(_SF_SIGS)
-
-for _name, (_res, _args) in _SF_SIGS.items():
-    _fn = getattr(sflib, _name)        # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# The closed-form kernel of DPC is a third companion library (include/fiat_amd_dpc.h), loaded and bound like the other two.
-# No fallback: a missing companion fails the import.
-DPC_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_dpc.so")
-if not os.path.exists(DPC_LIB_PATH):
-    raise ImportError(
-        f"{DPC_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
-
-dpclib = ctypes.CDLL(DPC_LIB_PATH)
-
+# DPC in closed form
 _DPC_SIGS = {
     "fx_dpc_abi_version": (c_int, []),
     "fx_dpc_descriptor": (c_int, [c_int, c_int, c_void_p]),
@@ -205,23 +168,7 @@ _DPC_SIGS = {
                                       c_void_p]),
 }
 
-DPC_EXPORTS = tuple(_DPC_SIGS)
-
-for _name, (_res, _args) in _DPC_SIGS.items():
-    _fn = getattr(dpclib, _name)       # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# The fused facet kernel of the H(div) trace element is a fourth companion library (include/fiat_amd_trace.h), loaded and
-# bound like the other three.  No fallback: a missing companion fails the import.
-TRACE_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_trace.so")
-if not os.path.exists(TRACE_LIB_PATH):
-    raise ImportError(
-        f"{TRACE_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
-
-tracelib = ctypes.CDLL(TRACE_LIB_PATH)
-
+# the fused facet kernel of the H(div) trace element
 _TRACE_SIGS = {
     "fx_trace_abi_version": (c_int, []),
     "fx_trace_kernel": (c_int, [c_int, c_int, c_int, c_int, c_char_p, c_int]),
@@ -229,24 +176,7 @@ _TRACE_SIGS = {
                                         c_int64, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
-TRACE_EXPORTS = tuple(_TRACE_SIGS)
-
-for _name, (_res, _args) in _TRACE_SIGS.items():
-    _fn = getattr(tracelib, _name)     # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-
-# The direct C0-hierarchy kernel of IntegratedLegendre is a fifth companion library (include/fiat_amd_hier.h), loaded and
-# bound like the other four.  No fallback: a missing companion fails the import.
-HIER_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_hier.so")
-if not os.path.exists(HIER_LIB_PATH):
-    raise ImportError(
-        f"{HIER_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
-
-hierlib = ctypes.CDLL(HIER_LIB_PATH)
-
+# the direct C0-hierarchy kernel of IntegratedLegendre
 _HIER_SIGS = {
     "fx_hier_abi_version": (c_int, []),
     "fx_hier_descriptor": (c_int, [c_int, c_int, c_void_p]),
@@ -255,24 +185,7 @@ _HIER_SIGS = {
                                        c_void_p, c_void_p]),
 }
 
-HIER_EXPORTS = tuple(_HIER_SIGS)
-
-for _name, (_res, _args) in _HIER_SIGS.items():
-    _fn = getattr(hierlib, _name)      # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-
-# The fused evaluation kernel (dof vectors in, values out) is a sixth companion library (include/fiat_amd_eval.h), loaded and
-# bound like the other five.  No fallback: a missing companion fails the import.
-EVAL_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd_eval.so")
-if not os.path.exists(EVAL_LIB_PATH):
-    raise ImportError(
-        f"{EVAL_LIB_PATH} not found: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()'); fiat_amd has no CPU fallback")
-
-evallib = ctypes.CDLL(EVAL_LIB_PATH)
-
+# the fused evaluation kernel (dof vectors in, values out)
 _EVAL_SIGS = {
     "fx_eval_abi_version": (c_int, []),
     "fx_eval_walk_order": (c_int, [c_int, c_int, c_void_p]),
@@ -285,12 +198,26 @@ _EVAL_SIGS = {
                               c_void_p]),
 }
 
-EVAL_EXPORTS = tuple(_EVAL_SIGS)
+SER_LIB_PATH, serlib, SER_EXPORTS = _load_companion("serendipity", _SER_SIGS)
+SF_LIB_PATH, sflib, SF_EXPORTS = _load_companion("sforms", _SF_SIGS)
+DPC_LIB_PATH, dpclib, DPC_EXPORTS = _load_companion("dpc", _DPC_SIGS)
+TRACE_LIB_PATH, tracelib, TRACE_EXPORTS = _load_companion("trace", _TRACE_SIGS)
+HIER_LIB_PATH, hierlib, HIER_EXPORTS = _load_companion("hier", _HIER_SIGS)
+EVAL_LIB_PATH, evallib, EVAL_EXPORTS = _load_companion("eval", _EVAL_SIGS)
 
-for _name, (_res, _args) in _EVAL_SIGS.items():
-    _fn = getattr(evallib, _name)      # AttributeError here = ABI mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
+# the main library the companions are linked against (its error slot): ``lib`` itself unless FIAT_AMD_LIB overrides that
+_DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd.so")
+_companion_main = lib if os.path.realpath(LIB_PATH) == os.path.realpath(_DEFAULT_LIB_PATH) else ctypes.CDLL(_DEFAULT_LIB_PATH)
+_companion_main.fx_last_error.restype = c_char_p
+_companion_main.fx_last_error.argtypes = []
+
+
+def companion_check(rc):
+    """``check`` for the companions' entries."""
+    return check(rc, _companion_main)
+
+
+ser_check = companion_check   # the name from when the Serendipity library was the only companion; existing callers keep working
 
 
 def check(rc, errlib=None):

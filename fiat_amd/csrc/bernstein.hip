@@ -3,37 +3,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "../../include/fiat_amd.h"
 #include "bernstein.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define BERN_HIP_TRY(expr)                                                        \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 constexpr int BERN_MAX_ORDER = 8;        // on the element's own cell
 constexpr int BERN_MAX_ORDER_CELLS = 4;  // with per-request cells (the chain-rule coefficients of every request in LDS)
@@ -86,33 +63,15 @@ bool host_bary(int sd, const double* v, double* E, double* v0, double* G) {
     return true;
 }
 
-template <int SD, int N> hipError_t launch_n(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::BernArgs& a) {
-    if (order == 0) hipLaunchKernelGGL((fxk::tabulate_bernstein<SD, N, 0>), grid, dim3(64), lds, s, a);
-    else if (order == 1) hipLaunchKernelGGL((fxk::tabulate_bernstein<SD, N, 1>), grid, dim3(64), lds, s, a);
-    else hipLaunchKernelGGL((fxk::tabulate_bernstein<SD, N, 2>), grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int SD> hipError_t launch_sd(int n, int order, dim3 grid, size_t lds, hipStream_t s, const fxk::BernArgs& a) {
-    switch (n) {
-        case 0: return launch_n<SD, 0>(order, grid, lds, s, a);
-        case 1: return launch_n<SD, 1>(order, grid, lds, s, a);
-        case 2: return launch_n<SD, 2>(order, grid, lds, s, a);
-        case 3: return launch_n<SD, 3>(order, grid, lds, s, a);
-        case 4: return launch_n<SD, 4>(order, grid, lds, s, a);
-        case 5: return launch_n<SD, 5>(order, grid, lds, s, a);
-        default: return launch_n<SD, 6>(order, grid, lds, s, a);
-    }
-}
-
-template <int SD> hipError_t launch_generic(dim3 grid, size_t lds, hipStream_t s, const fxk::BernArgs& a) {
-    const void* kern = reinterpret_cast<const void*>(fxk::tabulate_bernstein_generic<SD>);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fxk::tabulate_bernstein_generic<SD>, grid, dim3(64), lds, s, a);
-    return hipGetLastError();
+hipError_t launch(bool spec, int sd, int n, int order, unsigned grid, size_t lds, hipStream_t s, const fxk::BernArgs& a) {
+    return dispatch_int<1, 3>(sd, [&](auto SD) {
+        if (!spec) return launch_wave64(fxk::tabulate_bernstein_generic<SD()>, grid, lds, s, a);
+        return dispatch_int<0, fxk::BERN_SPEC_MAXN>(n, [&](auto N) {
+            return dispatch_int<0, 2>(order, [&](auto ORDER) {
+                return launch_wave64(fxk::tabulate_bernstein<SD(), N(), ORDER()>, grid, lds, s, a);
+            });
+        });
+    });
 }
 
 int bernstein_launch(const char* who, fx_ctx* ctx, int sd, int n, const double* cell, int order, int64_t nreq, int npts,
@@ -147,17 +106,14 @@ int bernstein_launch(const char* who, fx_ctx* ctx, int sd, int n, const double* 
     a.ntab = ntab;
     a.ndof = ndof;
     a.shared = shared ? 1 : 0;
-    int P = npts <= 64 ? 64 / npts : 1;
     const bool spec = n <= fxk::BERN_SPEC_MAXN && order <= 2;
-    size_t lds = 0;
-    long long gridcap;
+    const ItemPlan ip = plan_items(npts, reqsize, fxk::BERN_IMAGE_BYTES, false);  // (the generic instance takes its P only)
+    int P = ip.P, per_cu = 64;
+    size_t lds;
     if (spec) {
-        a.image = (long long)P * reqsize * 8 <= fxk::BERN_IMAGE_BYTES ? 1 : 0;
-        if (a.image) {
-            a.stage_doubles = (int)(((long long)P * reqsize + 1) & ~1LL);
-            lds = (size_t)a.stage_doubles * 8;
-        }
-        gridcap = (long long)num_cu * 64;
+        a.image = ip.image;
+        lds = ip.image_bytes;
+        a.stage_doubles = (int)(lds / 8);
     } else {
         const int csize = fxk::bern_coef_size(sd, order);
         if (cells) {  // one coefficient block per request of the item
@@ -168,21 +124,12 @@ int bernstein_launch(const char* who, fx_ctx* ctx, int sd, int n, const double* 
         }
         lds = (size_t)a.stage_doubles * 8;
         if ((long long)lds > lds_per_cu) return fail(FX_ENOTIMPL, "%s: %zu B of chain-rule coefficients exceed the LDS", who, lds);
-        gridcap = (long long)num_cu * 8;
+        per_cu = 8;
     }
     a.P = P;
     a.nitems = (nreq + P - 1) / P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, gridcap)));
-    BERN_HIP_TRY(hipSetDevice(device));
-    const hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    if (spec) {
-        e = sd == 1 ? launch_sd<1>(n, order, grid, lds, s, a) : sd == 2 ? launch_sd<2>(n, order, grid, lds, s, a)
-                                                                   : launch_sd<3>(n, order, grid, lds, s, a);
-    } else {
-        e = sd == 1 ? launch_generic<1>(grid, lds, s, a) : sd == 2 ? launch_generic<2>(grid, lds, s, a) : launch_generic<3>(grid, lds, s, a);
-    }
-    BERN_HIP_TRY(e);
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(launch(spec, sd, n, order, item_grid(a.nitems, num_cu, per_cu), lds, (hipStream_t)stream, a));
     return FX_OK;
 }
 

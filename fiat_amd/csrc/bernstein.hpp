@@ -8,7 +8,7 @@
 //
 // Lane <-> (request, point); an item is P whole requests (P * npts <= 64, or one request in chunks of 64 points).  Where
 // the item's tables fit (BERN_IMAGE_BYTES) they go through a per-wave LDS image and leave as whole-line non-temporal
-// stores (store.hpp flush_block); larger requests stream: every lane stores its own entries, row by row, with plain
+// stores (store.hpp flush_item); larger requests stream: every lane stores its own entries, row by row, with plain
 // stores.  Powers are repeated products, so an exponent 0 is exactly 1 at lambda = 0.
 //
 // Three sources of (lambda, G), set by the arguments:
@@ -43,12 +43,6 @@ struct BernArgs {
     int stage_doubles;    // per-wave LDS doubles of the image (generic: of the chain-rule coefficients)
     int shared;
 };
-
-__device__ __forceinline__ void bern_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 constexpr int bern_binom(int a, int b) {
     if (b < 0 || a < b) return 0;
@@ -198,17 +192,7 @@ __device__ __forceinline__ void bern_items(const BernArgs& a, double* stage, Bod
             const int pl = active ? slot - rl * npts : 0;
             body(r0 + rl, (size_t)rl * reqsize + pl, active, gout);
         }
-        if (a.image) {
-            bern_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double bv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<bv2d*>(gout), reinterpret_cast<const bv2d*>(stage), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = stage[i];
-            }
-            bern_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, stage, (long long)Pcur * reqsize, lane);
     }
 }
 
@@ -385,7 +369,7 @@ __device__ __forceinline__ void bern_chain_coefs(double* c, const double (&G)[SD
     if (lane0 == 0) c[0] = 1.0;
     int off_prev = 0, off = 1;
     for (int o = 1; o <= order; ++o) {
-        bern_lds_fence();
+        wave_lds_fence();
         const int nt = bern_binom(o + SD - 1, SD - 1), nb = bern_binom(o + SD, SD);
         const int nbp = bern_binom(o - 1 + SD, SD);
         for (int e = lane0; e < nt * nb; e += nl) {
@@ -424,7 +408,7 @@ __device__ __forceinline__ void bern_chain_coefs(double* c, const double (&G)[SD
         off_prev = off;
         off += nt * nb;
     }
-    bern_lds_fence();
+    wave_lds_fence();
 }
 
 template <int SD>
@@ -465,9 +449,9 @@ __global__ __launch_bounds__(64) void tabulate_bernstein_generic(const BernArgs 
                 // the coefficients of request rl: built by its lane of point 0 (npts <= 64 here, all requests of the
                 // item are in this pass)
                 double* cr = lds + (size_t)rl * csize;
-                bern_lds_fence();  // the previous item is done reading
+                wave_lds_fence();  // the previous item is done reading
                 if (active && pl == 0) bern_chain_coefs<SD>(cr, G, order, 0, 1);
-                bern_lds_fence();
+                wave_lds_fence();
                 c = cr;
             }
             if (!active) continue;

@@ -12,7 +12,7 @@
 // coordinate in registers by the recurrence l_a = l_{a-1} (K t - a + 1) / a, then writes every dof and table.  The dof table
 // is a constexpr function of (SD, K); dofs are a fold over an integer sequence, so no private array is indexed at run time.
 // An item is P whole requests (P * npts <= 64; one request in chunks of 64 points beyond).  Where it fits DPC_IMAGE_BYTES it
-// goes through a per-wave LDS image and leaves as whole-line non-temporal stores (flush_block); larger requests stream:
+// goes through a per-wave LDS image and leaves as whole-line non-temporal stores (store.hpp flush_item); larger requests stream:
 // every lane stores its own entries with plain stores.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 
 namespace fxk {
 
-// 40 KB per wave, as serendipity.hpp: four one-wave workgroups share the 160 KB of a CU, one per SIMD
+// 40 KB per wave: four one-wave workgroups share the 160 KB of a CU, one per SIMD
 constexpr int DPC_IMAGE_BYTES = 40 * 1024;
 constexpr int DPC_MAXK = 6, DPC_MAXORDER = 2;  // compile-time instances
 
@@ -37,12 +37,6 @@ struct DpcArgs {
     int P;              // whole requests per item
     int image;          // 1: per-wave LDS image of the item, 0: streaming stores
 };
-
-__device__ __forceinline__ void dpc_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 __host__ __device__ constexpr int dpc_binom(int a, int b) {
     if (b < 0 || a < b) return 0;
@@ -247,17 +241,7 @@ __global__ __launch_bounds__(64) void dpc_kernel(const DpcArgs a) {
             dpc_all_dofs<SD, K, ORDER>(std::make_integer_sequence<int, NDOF>{}, L, G, a.image != 0, lds, (int)off, gout + off, rs,
                                        tstride);
         }
-        if (a.image) {
-            dpc_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double dv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<dv2d*>(gout), reinterpret_cast<const dv2d*>(lds), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = lds[i];
-            }
-            dpc_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, lds, (long long)Pcur * reqsize, lane);
     }
 }
 

@@ -4,18 +4,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/fiat_amd_eval.h"
 #include "evaluate.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 struct fx_eval_element {
     fx_ctx* ctx = nullptr;
@@ -27,24 +22,6 @@ struct fx_eval_element {
 };
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define EVAL_HIP_TRY(expr)                                                        \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 const double UFC_VERTS[3][12] = {{0, 1}, {0, 0, 1, 0, 0, 1}, {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1}};
 
@@ -99,19 +76,11 @@ int make_plan(const char* who, int sd, int degree, int order, int vdim, int ndof
     return FX_OK;
 }
 
-template <int SD, int ORDER, int VDIM>
-hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::EvalArgs& a, const double* pts, const double* verts,
-                      const double* dofs, const double* Ap, const double* coef, double* out) {
-    hipLaunchKernelGGL((fxk::eval_kernel<SD, ORDER, VDIM>), grid, dim3(64), lds, s, a, pts, verts, dofs, Ap, coef, out);
-    return hipGetLastError();
-}
-
-template <int SD, int VDIM>
-hipError_t launch_order(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::EvalArgs& a, const double* pts,
-                        const double* verts, const double* dofs, const double* Ap, const double* coef, double* out) {
-    if (order == 0) return launch_one<SD, 0, VDIM>(grid, lds, s, a, pts, verts, dofs, Ap, coef, out);
-    if (order == 1) return launch_one<SD, 1, VDIM>(grid, lds, s, a, pts, verts, dofs, Ap, coef, out);
-    return launch_one<SD, 2, VDIM>(grid, lds, s, a, pts, verts, dofs, Ap, coef, out);
+// (sd, vdim): value shape () or (sd,)
+template <int SD, int VDIM, class... Args> hipError_t launch_order(int order, unsigned grid, size_t lds, hipStream_t s, const Args&... args) {
+    return dispatch_int<0, fxk::EVAL_MAXORDER>(order, [&](auto ORDER) {
+        return launch_wave64(fxk::eval_kernel<SD, ORDER(), VDIM>, grid, lds, s, args...);
+    });
 }
 
 template <int SD> void cell_map(const double* v, double* A, double* b) { fxk::eval_cell_map<SD>(v, A, b); }
@@ -255,9 +224,9 @@ int fx_eval_batch(fx_ctx* ctx, const fx_eval_element* e, int mapping, int order,
     a.chunks = p.chunks;
     a.mapping = mapping;
     a.nitems = p.chunks > 1 ? nreq * p.chunks : (nreq + p.P - 1) / p.P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * fxk::EVAL_GRID_PER_CU)));
+    const unsigned grid = item_grid(a.nitems, num_cu, fxk::EVAL_GRID_PER_CU);
     hipStream_t s = (hipStream_t)stream;
-    EVAL_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(hipSetDevice(device));
     const bool vec = e->vdim > 1;
     hipError_t he;
     if (e->sd == 1) he = launch_order<1, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
@@ -265,7 +234,7 @@ int fx_eval_batch(fx_ctx* ctx, const fx_eval_element* e, int mapping, int order,
                                   : launch_order<2, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
     else he = vec ? launch_order<3, 3>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out)
                   : launch_order<3, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
-    EVAL_HIP_TRY(he);
+    FX_HIP_TRY(he);
     return FX_OK;
 }
 

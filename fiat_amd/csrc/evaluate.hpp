@@ -11,7 +11,8 @@
 // coefficients A'[ndof][vdim][nexp], columns in the order of the walk.  The bubble variant's C0 transform is folded into A' on
 // the host (eval_fold), so the kernel only ever walks the raw recurrence.  15 instances.
 //
-// Lane <-> (request, point), items of whole requests, per-wave LDS image and flush: those of dpc.hpp / hierarchical.hpp.  A
+// Lane <-> (request, point), items of whole requests and a per-wave LDS image as in dpc.hpp / hierarchical.hpp; the image is
+// per right-hand side, so the kernel flushes it itself (store.hpp flush_block) instead of through flush_item.  A
 // request of more than 64 points is chunked by points: an item is then one chunk of one request, every chunk RECOMPUTES w
 // (ndof * vdim * nexp / 64 FMAs per lane against nexp * ntab * vdim and the steps of the walk: a few per cent, and no wave
 // waits for another), and its rows, 64 consecutive doubles each, leave as full-width stores straight from the registers.
@@ -358,12 +359,6 @@ struct EvalArgs {
     int mapping;  // 0 affine, 1 covariant, 2 contravariant Piola
 };
 
-__device__ __forceinline__ void eval_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
 // LDS of one wave, in doubles: dofs of the item's requests (rounded up to EVAL_RB requests), w, the image
 __host__ __device__ constexpr int eval_lds_c(int P, int ndof) { return ((P + EVAL_RB - 1) / EVAL_RB * EVAL_RB * ndof + 1) & ~1; }
 __host__ __device__ constexpr int eval_lds_w(int P, int vn) { return (P * vn + 1) & ~1; }
@@ -426,7 +421,7 @@ __global__ __launch_bounds__(64) void eval_kernel(const EvalArgs a, const double
                 const int rr = idx / ndof;
                 cs[idx] = dofs[((size_t)(r0 + rr) * nrhs + j) * ndof + (idx - rr * ndof)];
             }
-            eval_lds_fence();
+            wave_lds_fence();
             // w[r][v][k] = sum_i c[r][i] A'[i][v][k]: lanes over (v, k), EVAL_RB requests per read of A'
             for (int x = lane; x < VN; x += 64) {
                 for (int rb = 0; rb < Pcur; rb += EVAL_RB) {
@@ -444,7 +439,7 @@ __global__ __launch_bounds__(64) void eval_kernel(const EvalArgs a, const double
                         if (rb + u < Pcur) ws[(rb + u) * VN + x] = s[u];
                 }
             }
-            eval_lds_fence();
+            wave_lds_fence();
             if (active) {
                 double acc[NTAB][VDIM];
 #pragma unroll
@@ -473,7 +468,7 @@ __global__ __launch_bounds__(64) void eval_kernel(const EvalArgs a, const double
                 }
             }
             if (whole) {
-                eval_lds_fence();
+                wave_lds_fence();
                 const int total = Pcur * NTAB * seg;
                 if (nrhs == 1) {  // the item is one contiguous block
                     double* g = out + (size_t)r0 * reqsize;
@@ -491,7 +486,7 @@ __global__ __launch_bounds__(64) void eval_kernel(const EvalArgs a, const double
                     }
                 }
             }
-            eval_lds_fence();  // the next right-hand side, or item, overwrites dofs, w and the image
+            wave_lds_fence();  // the next right-hand side, or item, overwrites dofs, w and the image
         }
     }
 }

@@ -4,81 +4,32 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "../../include/fiat_amd.h"
 #include "hdivcurl.hpp"
+#include "host_common.hpp"
 
 namespace fx {
-int set_error(int code, const char* msg);  // api.hip
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
 void line_facts(const fx_line_element* e, fxk::LineDesc* L);
 }  // namespace fx
 
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define HDC_HIP_TRY(expr)                                                         \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
-
-template <int SD, int K, int ORDER, int KIND, bool GRID>
-hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::HdcArgs& a) {
-    auto kern = fxk::hdivcurl_kernel<SD, K, ORDER, KIND, GRID>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int SD, int K, int ORDER>
-hipError_t launch_kind(int kind, bool grid_mode, dim3 grid, size_t lds, hipStream_t s, const fxk::HdcArgs& a) {
-    if (kind == fxk::HDC_DIV)
-        return grid_mode ? launch_one<SD, K, ORDER, fxk::HDC_DIV, true>(grid, lds, s, a) : launch_one<SD, K, ORDER, fxk::HDC_DIV, false>(grid, lds, s, a);
-    return grid_mode ? launch_one<SD, K, ORDER, fxk::HDC_CURL, true>(grid, lds, s, a) : launch_one<SD, K, ORDER, fxk::HDC_CURL, false>(grid, lds, s, a);
-}
-
-template <int SD, int K>
-hipError_t launch_order(int order, int kind, bool grid_mode, dim3 grid, size_t lds, hipStream_t s, const fxk::HdcArgs& a) {
-    if (order == 0) return launch_kind<SD, K, 0>(kind, grid_mode, grid, lds, s, a);
-    if (order == 1) return launch_kind<SD, K, 1>(kind, grid_mode, grid, lds, s, a);
-    return launch_kind<SD, K, 2>(kind, grid_mode, grid, lds, s, a);
-}
-
 // instances: quadrilaterals K = 1..4, hexahedra K = 1..3, orders 0..2
 constexpr int HDC_MAXK_QUAD = 4, HDC_MAXK_HEX = 3, HDC_MAX_ORDER = 2;
 
-hipError_t launch_shape(int sd, int K, int order, int kind, bool grid_mode, dim3 grid, size_t lds, hipStream_t s, const fxk::HdcArgs& a) {
-    if (sd == 2) {
-        switch (K) {
-            case 1: return launch_order<2, 1>(order, kind, grid_mode, grid, lds, s, a);
-            case 2: return launch_order<2, 2>(order, kind, grid_mode, grid, lds, s, a);
-            case 3: return launch_order<2, 3>(order, kind, grid_mode, grid, lds, s, a);
-            default: return launch_order<2, 4>(order, kind, grid_mode, grid, lds, s, a);
-        }
-    }
-    switch (K) {
-        case 1: return launch_order<3, 1>(order, kind, grid_mode, grid, lds, s, a);
-        case 2: return launch_order<3, 2>(order, kind, grid_mode, grid, lds, s, a);
-        default: return launch_order<3, 3>(order, kind, grid_mode, grid, lds, s, a);
-    }
+template <int SD, int MAXK>
+hipError_t launch_sd(int K, int order, int kind, bool grid_mode, unsigned grid, size_t lds, hipStream_t s, const fxk::HdcArgs& a) {
+    return dispatch_int<1, MAXK>(K, [&](auto KK) {
+        return dispatch_int<0, HDC_MAX_ORDER>(order, [&](auto ORDER) {
+            return dispatch_int<fxk::HDC_DIV, fxk::HDC_CURL>(kind, [&](auto KIND) {
+                return grid_mode ? launch_wave64(fxk::hdivcurl_kernel<SD, KK(), ORDER(), KIND(), true>, grid, lds, s, a)
+                                 : launch_wave64(fxk::hdivcurl_kernel<SD, KK(), ORDER(), KIND(), false>, grid, lds, s, a);
+            });
+        });
+    });
 }
 
 int hdivcurl_launch(const char* who, fx_ctx* ctx, int sd, int kind, const fx_line_element* C, const fx_line_element* D,
@@ -133,14 +84,14 @@ int hdivcurl_launch(const char* who, fx_ctx* ctx, int sd, int kind, const fx_lin
     a.npts = npts;
     a.q = q;
     a.ndof = ndof;
-    const int P = npts <= 64 ? 64 / npts : 1;
-    a.P = P;
-    a.image = (long long)P * reqsize * 8 <= fxk::HDC_IMAGE_BYTES ? 1 : 0;
-    const size_t lds = a.image ? (size_t)(((long long)P * reqsize + 1) & ~1LL) * 8 : 0;
-    a.nitems = (nreq + P - 1) / P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
-    HDC_HIP_TRY(hipSetDevice(device));
-    HDC_HIP_TRY(launch_shape(sd, K, order, kind, grid_mode, grid, lds, (hipStream_t)stream, a));
+    const ItemPlan ip = plan_items(npts, reqsize, fxk::HDC_IMAGE_BYTES, false);
+    a.P = ip.P;
+    a.image = ip.image;
+    a.nitems = (nreq + ip.P - 1) / ip.P;
+    const unsigned grid = item_grid(a.nitems, num_cu, 64);
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY((sd == 2 ? launch_sd<2, HDC_MAXK_QUAD>(K, order, kind, grid_mode, grid, ip.image_bytes, (hipStream_t)stream, a)
+                        : launch_sd<3, HDC_MAXK_HEX>(K, order, kind, grid_mode, grid, ip.image_bytes, (hipStream_t)stream, a)));
     return FX_OK;
 }
 
@@ -194,9 +145,9 @@ int fx_table_place_batch(fx_ctx* ctx, int ntab, int64_t nreq, int npts, int rows
     a.row_offset = row_offset;
     a.npts = npts;
     const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((total + 255) / 256, (long long)num_cu * 32)));
-    HDC_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(hipSetDevice(device));
     hipLaunchKernelGGL(fxk::table_place_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    HDC_HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 

@@ -12,7 +12,7 @@
 // registers (compile-time node counts), then writes every table and dof: the signed product into the block's component and
 // zeros into the other components.  Blocks, directions and dofs are compile-time loops, so no array is indexed at run time.
 // An item of P whole requests (P * npts <= 64; one request in chunks of 64 points beyond) goes through a per-wave LDS image
-// and leaves as whole-line non-temporal stores (flush_block) where it fits HDC_IMAGE_BYTES; larger requests stream: every
+// and leaves as whole-line non-temporal stores (store.hpp flush_item) where it fits HDC_IMAGE_BYTES; larger requests stream: every
 // lane stores its own entries with plain stores, and the L2 joins the partial lines of neighbouring lanes and rows.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,12 +36,6 @@ struct HdcArgs {
     int P;              // whole requests per item
     int image;          // 1: per-wave LDS image of the item, 0: streaming stores
 };
-
-__device__ __forceinline__ void hdc_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // is direction d of block c the K+1-node factor C?
 template <int KIND> constexpr bool hdc_is_c(int c, int d) { return KIND == HDC_DIV ? d == c : d != c; }
@@ -148,17 +142,7 @@ __global__ __launch_bounds__(64) void hdivcurl_kernel(const HdcArgs a) {
             if constexpr (SD == 3)
                 if (a.off[2] >= 0) hdc_block<SD, K, ORDER, KIND, 2>(TC, TD, a.sign[2], base + a.off[2] * rs, np, rs, ts);
         }
-        if (a.image) {
-            hdc_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double hv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<hv2d*>(gout), reinterpret_cast<const hv2d*>(lds), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = lds[i];
-            }
-            hdc_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, lds, (long long)Pcur * reqsize, lane);
     }
 }
 

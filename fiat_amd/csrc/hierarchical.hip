@@ -4,38 +4,15 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/fiat_amd_hier.h"
 #include "hierarchical.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define HIER_HIP_TRY(expr)                                                        \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 // which route a shape takes
 struct HierPlan {
@@ -53,39 +30,21 @@ int make_plan(const char* who, int sd, int degree, int order, int npts, HierPlan
     p->ntab = fxk::hier_binom(sd + order, sd);
     p->reqsize = (long long)p->ntab * p->ndof * npts;
     if (p->reqsize >= (1LL << 31)) return fail(FX_ENOTIMPL, "%s: request of %lld entries", who, p->reqsize);
-    const int whole = npts > 0 && npts <= 64 ? 64 / npts : 1;  // whole requests per 64 lanes
-    p->P = whole;
-    p->image = 0;
-    p->lds = 0;
-    if (p->reqsize > 0 && p->reqsize * 8 <= fxk::HIER_IMAGE_BYTES) {
-        // the item shrinks to the requests whose tables fit the image
-        p->image = 1;
-        p->P = (int)std::min<long long>(whole, fxk::HIER_IMAGE_BYTES / (p->reqsize * 8));
-        p->lds = (size_t)(((long long)p->P * p->reqsize + 1) & ~1LL) * 8;
-    }
+    const ItemPlan ip = plan_items(npts, p->reqsize, fxk::HIER_IMAGE_BYTES, true);
+    p->P = ip.P;
+    p->image = ip.image;
+    p->lds = ip.image_bytes;
     return FX_OK;
 }
 
-template <int SD, int K, int ORDER> hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::HierArgs& a) {
-    hipLaunchKernelGGL((fxk::hier_kernel<SD, K, ORDER>), grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int SD, int K> hipError_t launch_order(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::HierArgs& a) {
-    if (order == 0) return launch_one<SD, K, 0>(grid, lds, s, a);
-    if (order == 1) return launch_one<SD, K, 1>(grid, lds, s, a);
-    return launch_one<SD, K, 2>(grid, lds, s, a);
-}
-
-template <int SD> hipError_t launch_degree(int K, int order, dim3 grid, size_t lds, hipStream_t s, const fxk::HierArgs& a) {
-    switch (K) {
-        case 1: return launch_order<SD, 1>(order, grid, lds, s, a);
-        case 2: return launch_order<SD, 2>(order, grid, lds, s, a);
-        case 3: return launch_order<SD, 3>(order, grid, lds, s, a);
-        case 4: return launch_order<SD, 4>(order, grid, lds, s, a);
-        case 5: return launch_order<SD, 5>(order, grid, lds, s, a);
-        default: return launch_order<SD, 6>(order, grid, lds, s, a);
-    }
+hipError_t launch(int sd, int degree, int order, unsigned grid, size_t lds, hipStream_t s, const fxk::HierArgs& a) {
+    return dispatch_int<1, 3>(sd, [&](auto SD) {
+        return dispatch_int<1, fxk::HIER_MAXK>(degree, [&](auto K) {
+            return dispatch_int<0, fxk::HIER_MAXORDER>(order, [&](auto ORDER) {
+                return launch_wave64(fxk::hier_kernel<SD(), K(), ORDER()>, grid, lds, s, a);
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -161,11 +120,8 @@ int fx_hier_tabulate_batch(fx_ctx* ctx, int sd, int degree, int order, const dou
     a.P = p.P;
     a.image = p.image;
     a.nitems = (nreq + p.P - 1) / p.P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
-    HIER_HIP_TRY(hipSetDevice(device));
-    HIER_HIP_TRY(sd == 1   ? launch_degree<1>(degree, order, grid, p.lds, (hipStream_t)stream, a)
-                 : sd == 2 ? launch_degree<2>(degree, order, grid, p.lds, (hipStream_t)stream, a)
-                           : launch_degree<3>(degree, order, grid, p.lds, (hipStream_t)stream, a));
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(launch(sd, degree, order, item_grid(a.nitems, num_cu, 64), p.lds, (hipStream_t)stream, a));
     return FX_OK;
 }
 

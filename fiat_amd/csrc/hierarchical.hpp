@@ -6,7 +6,8 @@
 // coefficient contraction: it is the integrated-Jacobi Dubiner recurrence (expansions.py:140-267, variant "bubble"), the
 // corrections that turn members into vertex, edge and face functions, and one multiplication per entry.
 //
-// Lane <-> (request, point), items, image / streaming routes and the flush are those of dpc.hpp.  The recurrence is a
+// Lane <-> (request, point) and the image / streaming routes are those of dpc.hpp; the item plan is host_common.hpp
+// plan_items, the flush store.hpp flush_item.  The recurrence is a
 // depth-first walk unrolled at compile time: the p-chain, per p the q-chain, per (p, q) the r-chain, two live members per
 // level.  Members are kept in their final normalisation (the ratios of the level norms are folded into the step
 // coefficients, as plan.hpp does on the host), coefficients and output rows are compile-time constants.
@@ -27,7 +28,7 @@
 
 namespace fxk {
 
-constexpr int HIER_IMAGE_BYTES = 40 * 1024;      // per wave, as dpc.hpp
+constexpr int HIER_IMAGE_BYTES = 40 * 1024;      // per wave: four one-wave workgroups per CU
 constexpr int HIER_MAXK = 6, HIER_MAXORDER = 2;  // compile-time instances
 
 struct HierArgs {
@@ -42,12 +43,6 @@ struct HierArgs {
     int P;      // whole requests per item
     int image;  // 1: per-wave LDS image of the item, 0: streaming stores
 };
-
-__device__ __forceinline__ void hier_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 __host__ __device__ constexpr int hier_binom(int a, int b) {
     if (b < 0 || a < b) return 0;
@@ -492,17 +487,7 @@ __global__ __launch_bounds__(64) void hier_kernel(const HierArgs a) {
             w.tstride = tstride;
             w.run();
         }
-        if (a.image) {
-            hier_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double dv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<dv2d*>(gout), reinterpret_cast<const dv2d*>(lds), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = lds[i];
-            }
-            hier_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, lds, (long long)Pcur * reqsize, lane);
     }
 }
 

@@ -3,38 +3,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/fiat_amd_serendipity.h"
 #include "serendipity.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define SER_HIP_TRY(expr)                                                         \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 // which instance and route a shape takes
 struct SerPlan {
@@ -55,51 +32,23 @@ int make_plan(const char* who, int sd, int degree, int order, int npts, SerPlan*
     p->reqsize = (long long)p->ntab * p->ndof * npts;
     if (p->reqsize >= (1LL << 31)) return fail(FX_ENOTIMPL, "%s: request of %lld entries", who, p->reqsize);
     p->generic = degree > fxk::SER_SPEC_MAXK || order > fxk::SER_SPEC_MAXORDER;
-    const int whole = npts > 0 && npts <= 64 ? 64 / npts : 1;  // whole requests per 64 lanes
-    p->P = whole;
-    p->image = 0;
-    p->lds = 0;
-    if (p->generic) {
-        p->lds = fxk::ser_generic_lds(sd, degree, order, p->ndof);
-    } else if (p->reqsize > 0 && p->reqsize * 8 <= fxk::SER_IMAGE_BYTES) {
-        // the item shrinks to the requests whose tables fit the image
-        p->image = 1;
-        p->P = (int)std::min<long long>(whole, fxk::SER_IMAGE_BYTES / (p->reqsize * 8));
-        p->lds = (size_t)(((long long)p->P * p->reqsize + 1) & ~1LL) * 8;
-    }
+    // (the generic instance streams: no image, its LDS holds the dof table and the lanes' 1-D tables)
+    const ItemPlan ip = plan_items(npts, p->reqsize, p->generic ? 0 : fxk::SER_IMAGE_BYTES, true);
+    p->P = ip.P;
+    p->image = ip.image;
+    p->lds = p->generic ? fxk::ser_generic_lds(sd, degree, order, p->ndof) : ip.image_bytes;
     return FX_OK;
 }
 
-template <int SD, int K, int ORDER> hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::SerArgs& a) {
-    hipLaunchKernelGGL((fxk::serendipity_kernel<SD, K, ORDER>), grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int SD, int K> hipError_t launch_order(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::SerArgs& a) {
-    if (order == 0) return launch_one<SD, K, 0>(grid, lds, s, a);
-    if (order == 1) return launch_one<SD, K, 1>(grid, lds, s, a);
-    return launch_one<SD, K, 2>(grid, lds, s, a);
-}
-
-template <int SD> hipError_t launch_degree(int K, int order, dim3 grid, size_t lds, hipStream_t s, const fxk::SerArgs& a) {
-    switch (K) {
-        case 1: return launch_order<SD, 1>(order, grid, lds, s, a);
-        case 2: return launch_order<SD, 2>(order, grid, lds, s, a);
-        case 3: return launch_order<SD, 3>(order, grid, lds, s, a);
-        case 4: return launch_order<SD, 4>(order, grid, lds, s, a);
-        case 5: return launch_order<SD, 5>(order, grid, lds, s, a);
-        default: return launch_order<SD, 6>(order, grid, lds, s, a);
-    }
-}
-
-template <int SD> hipError_t launch_generic(dim3 grid, size_t lds, hipStream_t s, const fxk::SerArgs& a) {
-    auto kern = fxk::serendipity_generic<SD>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
-    return hipGetLastError();
+hipError_t launch(bool generic, int sd, int degree, int order, unsigned grid, size_t lds, hipStream_t s, const fxk::SerArgs& a) {
+    return dispatch_int<2, 3>(sd, [&](auto SD) {
+        if (generic) return launch_wave64(fxk::serendipity_generic<SD()>, grid, lds, s, a);
+        return dispatch_int<1, fxk::SER_SPEC_MAXK>(degree, [&](auto K) {
+            return dispatch_int<0, fxk::SER_SPEC_MAXORDER>(order, [&](auto ORDER) {
+                return launch_wave64(fxk::serendipity_kernel<SD(), K(), ORDER()>, grid, lds, s, a);
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -174,10 +123,8 @@ int fx_serendipity_tabulate_batch(fx_ctx* ctx, int sd, int degree, const double*
     a.degree = degree;
     a.order = order;
     a.nitems = (nreq + p.P - 1) / p.P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
-    SER_HIP_TRY(hipSetDevice(device));
-    if (p.generic) SER_HIP_TRY(sd == 2 ? launch_generic<2>(grid, p.lds, (hipStream_t)stream, a) : launch_generic<3>(grid, p.lds, (hipStream_t)stream, a));
-    else SER_HIP_TRY(sd == 2 ? launch_degree<2>(degree, order, grid, p.lds, (hipStream_t)stream, a) : launch_degree<3>(degree, order, grid, p.lds, (hipStream_t)stream, a));
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(launch(p.generic, sd, degree, order, item_grid(a.nitems, num_cu, 64), p.lds, (hipStream_t)stream, a));
     return FX_OK;
 }
 

@@ -13,7 +13,7 @@
 // writes every table and dof.  The dof table is a constexpr function of (SD, K); tables and dofs are compile-time loops, so
 // no private array is indexed at run time.  An item is P whole requests (P * npts <= 64; one request in chunks of 64 points
 // beyond).  Where it fits SER_IMAGE_BYTES it goes through a per-wave LDS image and leaves as whole-line non-temporal stores
-// (flush_block); larger requests stream: every lane stores its own entries with plain stores.
+// (store.hpp flush_item); larger requests stream: every lane stores its own entries with plain stores.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +24,7 @@
 
 namespace fxk {
 
-// 40 KB per wave, as hdivcurl.hpp: four one-wave workgroups share the 160 KB of a CU, one per SIMD
+// 40 KB per wave: four one-wave workgroups share the 160 KB of a CU, one per SIMD
 constexpr int SER_IMAGE_BYTES = 40 * 1024;
 constexpr int SER_SPEC_MAXK = 6, SER_SPEC_MAXORDER = 2;  // compile-time instances
 constexpr int SER_GEN_MAXK = 12, SER_GEN_MAXORDER = 3;   // generic instance
@@ -39,12 +39,6 @@ struct SerArgs {
     int image;          // 1: per-wave LDS image of the item, 0: streaming stores
     int degree, order;  // generic instance only
 };
-
-__device__ __forceinline__ void ser_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // ---- the dof table ------------------------------------------------------------------------------------------------------
 // One packed row per dof, in FIAT's order: bit 0 = the sign is minus, bits 8.., 16.., 24.. = the codes of x, y, z.
@@ -234,17 +228,7 @@ __global__ __launch_bounds__(64) void serendipity_kernel(const SerArgs a) {
             double* base = (a.image ? lds : gout) + (size_t)rl * reqsize + pl;
             ser_tables<SD, K, ORDER>(std::make_integer_sequence<int, NTAB>{}, F, base, rs);
         }
-        if (a.image) {
-            ser_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double sv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<sv2d*>(gout), reinterpret_cast<const sv2d*>(lds), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = lds[i];
-            }
-            ser_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, lds, (long long)Pcur * reqsize, lane);
     }
 }
 
@@ -266,7 +250,7 @@ __global__ __launch_bounds__(64) void serendipity_generic(const SerArgs a) {
     int* rows = reinterpret_cast<int*>(lds);
     double* T = lds + (ndof + 1) / 2;
     if (lane == 0) ser_fill(SD, K, rows);
-    ser_lds_fence();
+    wave_lds_fence();
     const size_t tstride = (size_t)ndof * npts;
     const long long reqsize = (long long)a.ntab * tstride;
     for (long long item = blockIdx.x; item < a.nitems; item += gridDim.x) {

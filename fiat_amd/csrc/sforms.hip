@@ -3,18 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "../../include/fiat_amd_sforms.h"
 #include "sforms.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 struct fx_sforms_element {
     int device, sd, degree, nrows;
@@ -23,24 +18,6 @@ struct fx_sforms_element {
 };
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define SF_HIP_TRY(expr)                                                          \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 // which route a shape takes
 struct SfPlan {
@@ -66,32 +43,19 @@ int make_plan(const char* who, int sd, int degree, int nrows, int order, int npt
     p->reqsize = (long long)p->ntab * nrows * sd * npts;
     if (p->reqsize >= (1LL << 31)) return fail(FX_ENOTIMPL, "%s: request of %lld entries", who, p->reqsize);
     p->budget = fxk::sf_image_budget(sd, degree, order);
-    p->P = npts > 0 && npts <= 64 ? 64 / npts : 1;  // whole requests per 64 lanes
-    p->image = 0;
-    p->lds = fxk::sf_tables_bytes(sd, degree, order);
-    if (p->reqsize > 0 && p->reqsize * 8 <= p->budget) {
-        // the item shrinks to the requests whose tables fit the image
-        p->image = 1;
-        p->P = (int)std::min<long long>(p->P, p->budget / (p->reqsize * 8));
-        p->lds += (size_t)(((long long)p->P * p->reqsize + 1) & ~1LL) * 8;
-    }
+    const ItemPlan ip = plan_items(npts, p->reqsize, p->budget, true);
+    p->P = ip.P;
+    p->image = ip.image;
+    p->lds = fxk::sf_tables_bytes(sd, degree, order) + ip.image_bytes;  // the 1-D tables, then the image
     return FX_OK;
 }
 
-template <int SD, int ORDER> hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::SfArgs& a) {
-    auto kern = fxk::sforms_kernel<SD, ORDER>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int SD> hipError_t launch_order(int order, dim3 grid, size_t lds, hipStream_t s, const fxk::SfArgs& a) {
-    if (order == 0) return launch_one<SD, 0>(grid, lds, s, a);
-    if (order == 1) return launch_one<SD, 1>(grid, lds, s, a);
-    return launch_one<SD, 2>(grid, lds, s, a);
+hipError_t launch(int sd, int order, unsigned grid, size_t lds, hipStream_t s, const fxk::SfArgs& a) {
+    return dispatch_int<2, 3>(sd, [&](auto SD) {
+        return dispatch_int<0, fxk::SF_MAXORDER>(order, [&](auto ORDER) {
+            return launch_wave64(fxk::sforms_kernel<SD(), ORDER()>, grid, lds, s, a);
+        });
+    });
 }
 
 }  // namespace
@@ -125,7 +89,7 @@ int fx_sforms_element_create(fx_ctx* ctx, int sd, int degree, int nrows, const d
     }
     int device = 0, num_cu = 0, lds_per_cu = 0;
     fx::ctx_facts(ctx, &device, &num_cu, &lds_per_cu);
-    SF_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(hipSetDevice(device));
     fx_sforms_element* el = new fx_sforms_element{device, sd, degree, nrows, nullptr, nullptr};
     hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&el->coef), npad * sizeof(double));
     hipError_t e2 = e1 == hipSuccess ? hipMalloc(reinterpret_cast<void**>(&el->codes), npad * sizeof(int)) : e1;
@@ -194,9 +158,8 @@ int fx_sforms_tabulate_batch(fx_ctx* ctx, const fx_sforms_element* el, const dou
     a.image = p.image;
     a.degree = el->degree;
     a.nitems = (nreq + p.P - 1) / p.P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
-    SF_HIP_TRY(hipSetDevice(device));
-    SF_HIP_TRY(el->sd == 2 ? launch_order<2>(order, grid, p.lds, (hipStream_t)stream, a) : launch_order<3>(order, grid, p.lds, (hipStream_t)stream, a));
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(launch(el->sd, order, item_grid(a.nitems, num_cu, 64), p.lds, (hipStream_t)stream, a));
     return FX_OK;
 }
 

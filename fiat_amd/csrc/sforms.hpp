@@ -16,7 +16,7 @@
 // walks tables, dofs and components: a nonzero entry is the coefficient times SD LDS reads, a zero entry is stored without
 // reads.  An item is P whole requests (P * npts <= 64; one request in chunks of 64 points beyond).  Where it fits the image
 // budget it goes through a per-wave LDS image behind the 1-D tables and leaves as whole-line non-temporal stores
-// (flush_block); larger requests stream: every lane stores its own entries with plain stores.
+// (store.hpp flush_item); larger requests stream: every lane stores its own entries with plain stores.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,7 +28,7 @@ namespace fxk {
 constexpr int SF_MAXK = 6, SF_MAXORDER = 2;
 constexpr int SF_CHUNK = 4;  // entries of the term table fetched together; the device table is padded to a multiple
 // LDS of one (one-wave) workgroup: the 1-D tables, then the image.  While the tables leave room the workgroup stays at
-// 40 KB (four per CU, one per SIMD, as serendipity.hpp); larger tables keep a 16 KB image, which bounds the workgroup by
+// 40 KB (four per CU, one per SIMD); larger tables keep a 16 KB image, which bounds the workgroup by
 // 64 KB (two per CU at the worst).
 constexpr int SF_WG_BYTES = 40 * 1024, SF_MIN_IMAGE_BYTES = 16 * 1024;
 
@@ -55,12 +55,6 @@ struct SfArgs {
     int image;           // 1: per-wave LDS image of the item, 0: streaming stores
     int degree;
 };
-
-__device__ __forceinline__ void sf_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // this lane's 1-D tables of one direction: Td[(m nf + c) 64] = m-th derivative in x of the function of code c
 template <int ORDER>
@@ -180,17 +174,7 @@ __global__ __launch_bounds__(64) void sforms_kernel(const SfArgs a) {
                 }
             }
         }
-        if (a.image) {
-            sf_lds_fence();
-            const long long total = (long long)Pcur * reqsize;
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double sv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<sv2d*>(gout), reinterpret_cast<const sv2d*>(image), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = image[i];
-            }
-            sf_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, image, (long long)Pcur * reqsize, lane);
     }
 }
 

@@ -1,4 +1,4 @@
-// Output stores of the tabulation kernels (gfx950).
+// Output stores of the tabulation kernels and the phase fence of a wave (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ablation.hpp"
@@ -8,6 +8,17 @@
 #endif
 
 namespace fxk {
+
+__device__ __forceinline__ void wave_lds_fence() {
+    // LDS operations of one wave complete in order; this only stops the compiler from
+    // moving LDS accesses of different lanes across a phase boundary.  The fences are
+    // restricted to the LDS address space ("local"): an unrestricted release fence makes
+    // hipcc wait vmcnt(0), i.e. for every outstanding HBM store of the wave -- measured
+    // to serialise the store phase with the next request's compute.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
 
 // Output tables are written once and read by later kernels: non-temporal stores let the L2
 // stream them out instead of holding them as dirty lines until an eviction is forced
@@ -36,6 +47,20 @@ template <class V2> __device__ __forceinline__ void flush_block(V2* g2, const V2
     if (lane < head) g2[lane] = s2[lane];
     for (int i = head + lane; i < body_end; i += 64) stream_store(&g2[i], s2[i]);
     if (body_end + lane < nch) g2[body_end + lane] = s2[body_end + lane];
+}
+
+// One wave writes the LDS image of its item, `total` doubles that are contiguous in global memory from `gout`, and gives the
+// image back: as 16-byte chunks through flush_block where the block allows it (an even total from a 16-byte boundary; an
+// `out=` view or an odd request may start 8 bytes off), one double per lane and step otherwise.
+__device__ __forceinline__ void flush_item(double* gout, const double* img, long long total, int lane) {
+    wave_lds_fence();
+    if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
+        typedef double chunk __attribute__((ext_vector_type(2)));
+        flush_block(reinterpret_cast<chunk*>(gout), reinterpret_cast<const chunk*>(img), (int)(total >> 1), lane);
+    } else {
+        for (long long i = lane; i < total; i += 64) gout[i] = img[i];
+    }
+    wave_lds_fence();  // the next item overwrites the image
 }
 
 }  // namespace fxk

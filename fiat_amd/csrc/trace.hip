@@ -4,37 +4,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "../../include/fiat_amd_trace.h"
 #include "trace.hpp"
-
-namespace fx {
-int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so)
-void ctx_facts(const fx_ctx* ctx, int* device, int* num_cu, int* lds_per_cu);
-}  // namespace fx
+#include "host_common.hpp"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return fx::set_error(code, buf);
-}
-
-#define TRACE_HIP_TRY(expr)                                                       \
-    do {                                                                          \
-        hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) {                                                   \
-            (void)hipGetLastError();                                              \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
-        }                                                                         \
-    } while (0)
 
 // which instance and route a shape takes
 struct TracePlan {
@@ -54,18 +31,11 @@ int make_plan(const char* who, int fd, int degree, int nfac, int npts, TracePlan
     p->nf = fxk::trace_nf(fd, degree);
     p->reqsize = (long long)nfac * p->nf * npts;
     if (p->reqsize >= (1LL << 31)) return fail(FX_ENOTIMPL, "%s: request of %lld entries", who, p->reqsize);
-    const int whole = npts > 0 && npts <= 64 ? 64 / npts : 1;  // whole requests per 64 lanes
     const long long cbytes = p->K >= 0 ? (((long long)p->nf * p->nf + 1) & ~1LL) * 8 : 0;  // the LDS-resident matrix
-    const long long budget = fxk::TRACE_LDS_BYTES - cbytes;
-    p->P = whole;
-    p->image = 0;
-    p->lds = (size_t)cbytes;
-    if (p->reqsize > 0 && p->reqsize * 8 <= budget) {
-        // the item shrinks to the requests whose tables fit the image
-        p->image = 1;
-        p->P = (int)std::min<long long>(whole, budget / (p->reqsize * 8));
-        p->lds = (size_t)(cbytes + (((long long)p->P * p->reqsize + 1) & ~1LL) * 8);
-    }
+    const ItemPlan ip = plan_items(npts, p->reqsize, fxk::TRACE_LDS_BYTES - cbytes, true);
+    p->P = ip.P;
+    p->image = ip.image;
+    p->lds = (size_t)cbytes + ip.image_bytes;
     return FX_OK;
 }
 
@@ -84,30 +54,17 @@ fxk::TraceRec make_rec(int fd, int degree) {
     return rec;
 }
 
-template <int FD, int K> hipError_t launch_one(dim3 grid, size_t lds, hipStream_t s, const fxk::TraceArgs& a) {
-    if constexpr (K < 0) {
-        hipLaunchKernelGGL((fxk::trace_kernel<FD, K>), grid, dim3(64), lds, s, a, make_rec(FD, a.degree));
-    } else {
-        hipLaunchKernelGGL((fxk::trace_kernel<FD, K>), grid, dim3(64), lds, s, a, fxk::TraceNoRec{});
-    }
-    return hipGetLastError();
+template <int FD, int K> hipError_t launch_one(unsigned grid, size_t lds, hipStream_t s, const fxk::TraceArgs& a) {
+    if constexpr (K < 0) return launch_wave64(fxk::trace_kernel<FD, K>, grid, lds, s, a, make_rec(FD, a.degree));
+    else return launch_wave64(fxk::trace_kernel<FD, K>, grid, lds, s, a, fxk::TraceNoRec{});
 }
 
-template <int FD> hipError_t launch_degree(int K, dim3 grid, size_t lds, hipStream_t s, const fxk::TraceArgs& a) {
-    switch (K) {
-        case 0: return launch_one<FD, 0>(grid, lds, s, a);
-        case 1: return launch_one<FD, 1>(grid, lds, s, a);
-        case 2: return launch_one<FD, 2>(grid, lds, s, a);
-        case 3: return launch_one<FD, 3>(grid, lds, s, a);
-        case 4: return launch_one<FD, 4>(grid, lds, s, a);
-        case 5: return launch_one<FD, 5>(grid, lds, s, a);
-        case 6: return launch_one<FD, 6>(grid, lds, s, a);
-        default: return launch_one<FD, -1>(grid, lds, s, a);
-    }
-}
-
-template <> hipError_t launch_degree<0>(int, dim3 grid, size_t lds, hipStream_t s, const fxk::TraceArgs& a) {
-    return launch_one<0, 0>(grid, lds, s, a);  // a point carries the constant
+hipError_t launch(int fd, int K, unsigned grid, size_t lds, hipStream_t s, const fxk::TraceArgs& a) {
+    if (fd == 0) return launch_one<0, 0>(grid, lds, s, a);  // a point carries the constant
+    return dispatch_int<1, 2>(fd, [&](auto FD) {
+        if (K < 0) return launch_one<FD(), -1>(grid, lds, s, a);  // the run-time-degree instance
+        return dispatch_int<0, fxk::TRACE_MAXK>(K, [&](auto KK) { return launch_one<FD(), KK()>(grid, lds, s, a); });
+    });
 }
 
 }  // namespace
@@ -173,11 +130,8 @@ int fx_trace_tabulate_batch(fx_ctx* ctx, int fd, int degree, int nfac, int mode,
     a.degree = degree;
     a.swap = fd == 0;
     a.nitems = (nreq + p.P - 1) / p.P;
-    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(a.nitems, (long long)num_cu * 64)));
-    TRACE_HIP_TRY(hipSetDevice(device));
-    TRACE_HIP_TRY(fd == 0   ? launch_degree<0>(0, grid, p.lds, (hipStream_t)stream, a)
-                  : fd == 1 ? launch_degree<1>(p.K, grid, p.lds, (hipStream_t)stream, a)
-                            : launch_degree<2>(p.K, grid, p.lds, (hipStream_t)stream, a));
+    FX_HIP_TRY(hipSetDevice(device));
+    FX_HIP_TRY(launch(fd, p.K, item_grid(a.nitems, num_cu, 64), p.lds, (hipStream_t)stream, a));
     return FX_OK;
 }
 

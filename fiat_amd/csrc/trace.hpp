@@ -25,7 +25,7 @@
 // coefficients read from a kernel argument of its own (TraceRec) and matrix rows read through the scalar cache from L2.
 //
 // Output: where an item fits the image it is zeroed in LDS, the lanes write their facet blocks (or NaN columns) into it and
-// it leaves as whole-line non-temporal stores (flush_block); larger requests stream: every lane stores its own column, zeros
+// it leaves as whole-line non-temporal stores (store.hpp flush_item); larger requests stream: every lane stores its own column, zeros
 // included, with plain stores.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@
 
 namespace fxk {
 
-// LDS of one (one-wave) workgroup, matrix and image together: four workgroups share the 160 KB of a CU, as serendipity.hpp
+// LDS of one (one-wave) workgroup, matrix and image together: four workgroups share the 160 KB of a CU
 constexpr int TRACE_LDS_BYTES = 40 * 1024;
 constexpr int TRACE_MAXK = 6;      // compile-time instances: degree 0..6
 constexpr int TRACE_MAXGEN = 12;   // the run-time-degree instance
@@ -77,12 +77,6 @@ struct TraceArgs {
     int facet, nfac, degree;
     int swap;            // the interval: the point where lambda_i vanishes is facet 1 - i
 };
-
-__device__ __forceinline__ void trace_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // steps 1 and 2: the facet the point is on (false: none, or more than one) and its facet coordinates
 template <int FD> __device__ __forceinline__ bool trace_locate(const TraceArgs& a, const double* pp, int& f, double (&x)[FD + 1]) {
@@ -191,7 +185,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceArgs a, const Trac
     const double nan = __builtin_nan("");
     if constexpr (!GEN) {
         for (int i = lane; i < NF * NF; i += 64) lds[i] = a.C[i];
-        trace_lds_fence();
+        wave_lds_fence();
     }
     for (long long item = blockIdx.x; item < a.nitems; item += gridDim.x) {
         const long long r0 = item * a.P;
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceArgs a, const Trac
         }
         if (a.image) {
             for (long long i = lane; i < total; i += 64) img[i] = 0.0;
-            trace_lds_fence();
+            wave_lds_fence();
         }
         for (int s0 = 0; s0 < nslots; s0 += 64) {
             const int slot = s0 + lane;
@@ -290,16 +284,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceArgs a, const Trac
                 }
             }
         }
-        if (a.image) {
-            trace_lds_fence();
-            if ((total & 1) == 0 && (reinterpret_cast<unsigned long long>(gout) & 15ull) == 0) {
-                typedef double dv2d __attribute__((ext_vector_type(2)));
-                flush_block(reinterpret_cast<dv2d*>(gout), reinterpret_cast<const dv2d*>(img), (int)(total >> 1), lane);
-            } else {
-                for (long long i = lane; i < total; i += 64) gout[i] = img[i];
-            }
-            trace_lds_fence();  // the next item overwrites the image
-        }
+        if (a.image) flush_item(gout, img, total, lane);
     }
 }
 

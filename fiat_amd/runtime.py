@@ -619,21 +619,37 @@ def table_place(src, dst, row_offset, comp_src, comp_sign, ctx=None, stream=None
     return dst
 
 
+def _route(entry, *shape):
+    """Route string of an ``fx_*_kernel`` entry of a companion library (host only); shapes without an instance raise."""
+    buf = ctypes.create_string_buffer(160)
+    _lib.companion_check(entry(*(int(v) for v in shape), buf, len(buf)))
+    return buf.value.decode()
+
+
+def _out_or_new(out, shape, ctx, plan):
+    """``out`` if given and fit to be written, else a new tensor.  ``plan()`` is asked first: a shape without an instance
+    raises before anything is allocated."""
+    if out is None:
+        plan()
+        return torch.empty(shape, dtype=torch.float64, device=ctx.device)
+    if tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
+        raise ValueError("out has the wrong shape/dtype/layout")
+    return out
+
+
 def serendipity_descriptor(sd, degree):
     """The dof table of S_degree the kernels are compiled from (fx_serendipity_descriptor; host only): rows (sign, code_x,
     code_y[, code_z])."""
     ndof = c_int(0)
-    _lib.ser_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
+    _lib.companion_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
     rows = np.zeros((ndof.value, 1 + sd), dtype=np.int32)
-    _lib.ser_check(_lib.serlib.fx_serendipity_descriptor(int(sd), int(degree), host_ptr(rows)))
+    _lib.companion_check(_lib.serlib.fx_serendipity_descriptor(int(sd), int(degree), host_ptr(rows)))
     return rows
 
 
 def serendipity_kernel(sd, degree, order, npts):
     """Name of the kernel instance and output route a shape takes (fx_serendipity_kernel; host only)."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.serlib.fx_serendipity_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
-    return buf.value.decode()
+    return _route(_lib.serlib.fx_serendipity_kernel, sd, degree, order, npts)
 
 
 def serendipity_tabulate_batch(sd, degree, lo, hi, order, pts, out=None, stream=None, ctx=None):
@@ -649,18 +665,14 @@ def serendipity_tabulate_batch(sd, degree, lo, hi, order, pts, out=None, stream=
     if lo.shape != (sd,) or hi.shape != (sd,):
         raise ValueError("the box needs one lower and one upper coordinate per direction")
     ndof = c_int(0)
-    _lib.ser_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
+    _lib.companion_check(_lib.serlib.fx_serendipity_dims(int(sd), int(degree), ctypes.byref(ndof)))
     if order < 0:
         raise ValueError("negative derivative order")
     shape = (nreq, num_tables(sd, order), ndof.value, npts)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        serendipity_kernel(sd, degree, order, npts)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.serlib.fx_serendipity_tabulate_batch(ctx.handle, int(sd), int(degree), host_ptr(lo), host_ptr(hi), int(order),
-                                                    nreq, npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    out = _out_or_new(out, shape, ctx, lambda: serendipity_kernel(sd, degree, order, npts))
+    _lib.companion_check(_lib.serlib.fx_serendipity_tabulate_batch(
+        ctx.handle, int(sd), int(degree), host_ptr(lo), host_ptr(hi), int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out),
+        _stream_ptr(stream)))
     return out
 
 
@@ -668,16 +680,14 @@ def dpc_descriptor(sd, degree):
     """The dof table of DPC_degree the kernels are compiled from (fx_dpc_descriptor; host only): rows alpha, sd + 1 entries of
     sum ``degree``, in the order of the reference's nodes."""
     rows = np.zeros((math.comb(int(degree) + int(sd), int(sd)), sd + 1), dtype=np.int32)
-    _lib.ser_check(_lib.dpclib.fx_dpc_descriptor(int(sd), int(degree), host_ptr(rows)))
+    _lib.companion_check(_lib.dpclib.fx_dpc_descriptor(int(sd), int(degree), host_ptr(rows)))
     return rows
 
 
 def dpc_kernel(sd, degree, order, npts):
     """Kernel instance, output route and requests per item of a shape (fx_dpc_kernel; host only):
     ``"fxk::dpc_kernel<sd,degree,order> image|stream P=<p>"``."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.dpclib.fx_dpc_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
-    return buf.value.decode()
+    return _route(_lib.dpclib.fx_dpc_kernel, sd, degree, order, npts)
 
 
 def dpc_tabulate_batch(sd, degree, lam0, G, order, pts, out=None, stream=None, ctx=None):
@@ -696,14 +706,10 @@ def dpc_tabulate_batch(sd, degree, lam0, G, order, pts, out=None, stream=None, c
     if order < 0:
         raise ValueError("negative derivative order")
     shape = (nreq, num_tables(sd, order), math.comb(int(degree) + sd, sd), npts)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        dpc_kernel(sd, degree, order, npts)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.dpclib.fx_dpc_tabulate_batch(ctx.handle, int(sd), int(degree), host_ptr(lam0), host_ptr(G), int(order), nreq,
-                                                    npts, _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    out = _out_or_new(out, shape, ctx, lambda: dpc_kernel(sd, degree, order, npts))
+    _lib.companion_check(_lib.dpclib.fx_dpc_tabulate_batch(
+        ctx.handle, int(sd), int(degree), host_ptr(lam0), host_ptr(G), int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out),
+        _stream_ptr(stream)))
     return out
 
 
@@ -711,16 +717,14 @@ def hier_descriptor(sd, degree):
     """The dof table of IntegratedLegendre(degree) the kernels are compiled from (fx_hier_descriptor; host only): rows
     (p, q, r, entity dimension), in the order of the reference's dofs."""
     rows = np.zeros((math.comb(int(degree) + int(sd), int(sd)), 4), dtype=np.int32)
-    _lib.ser_check(_lib.hierlib.fx_hier_descriptor(int(sd), int(degree), host_ptr(rows)))
+    _lib.companion_check(_lib.hierlib.fx_hier_descriptor(int(sd), int(degree), host_ptr(rows)))
     return rows
 
 
 def hier_kernel(sd, degree, order, npts):
     """Kernel instance, output route and requests per item of a shape (fx_hier_kernel; host only):
     ``"fxk::hier_kernel<sd,degree,order> image|stream P=<p>"``."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.hierlib.fx_hier_kernel(int(sd), int(degree), int(order), int(npts), buf, len(buf)))
-    return buf.value.decode()
+    return _route(_lib.hierlib.fx_hier_kernel, sd, degree, order, npts)
 
 
 def hier_tabulate_batch(sd, degree, order, scales, A, b, pts, out=None, stream=None, ctx=None):
@@ -741,14 +745,10 @@ def hier_tabulate_batch(sd, degree, order, scales, A, b, pts, out=None, stream=N
     if order < 0:
         raise ValueError("negative derivative order")
     shape = (nreq, num_tables(sd, order), math.comb(int(degree) + sd, sd), npts)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        hier_kernel(sd, degree, order, npts)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.hierlib.fx_hier_tabulate_batch(ctx.handle, int(sd), int(degree), int(order), host_ptr(scales), _dev_ptr(pts),
-                                                      nreq, npts, _dev_ptr(out), _stream_ptr(stream), host_ptr(A), host_ptr(b)))
+    out = _out_or_new(out, shape, ctx, lambda: hier_kernel(sd, degree, order, npts))
+    _lib.companion_check(_lib.hierlib.fx_hier_tabulate_batch(
+        ctx.handle, int(sd), int(degree), int(order), host_ptr(scales), _dev_ptr(pts), nreq, npts, _dev_ptr(out),
+        _stream_ptr(stream), host_ptr(A), host_ptr(b)))
     return out
 
 
@@ -768,10 +768,10 @@ class EvalElement:
             raise ValueError(f"coefficients must have shape (ndof, *value_shape, {self.nexp})")
         cell = None if cell is None else np.ascontiguousarray(cell, dtype=np.float64).reshape(self.sd + 1, self.sd)
         h = c_void_p()
-        _lib.ser_check(_lib.evallib.fx_eval_element_create(self.ctx.handle, self.sd, self.degree, VARIANTS[variant],
-                                                          -1.0 if scale is None else float(scale),
-                                                          None if cell is None else host_ptr(cell), self.ndof, self.vdim,
-                                                          host_ptr(coeffs), ctypes.byref(h)))
+        _lib.companion_check(_lib.evallib.fx_eval_element_create(self.ctx.handle, self.sd, self.degree, VARIANTS[variant],
+                                                                  -1.0 if scale is None else float(scale),
+                                                                  None if cell is None else host_ptr(cell), self.ndof, self.vdim,
+                                                                  host_ptr(coeffs), ctypes.byref(h)))
         self.handle = h
 
     def __del__(self):
@@ -789,10 +789,7 @@ class EvalElement:
 def eval_kernel(sd, degree, order, vdim, ndof, npts, nrhs=1):
     """Kernel instance and item scheme of a shape (fx_eval_kernel; host only):
     ``"fxk::eval_kernel<sd,order,vdim> degree=<n> P=<requests per item> chunks=<point chunks per request>"``."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.evallib.fx_eval_kernel(int(sd), int(degree), int(order), int(vdim), int(ndof), int(npts), int(nrhs), buf,
-                                              len(buf)))
-    return buf.value.decode()
+    return _route(_lib.evallib.fx_eval_kernel, sd, degree, order, vdim, ndof, npts, nrhs)
 
 
 def eval_batch(elem, order, pts, dofs, verts=None, out=None, stream=None, mapping=None):
@@ -820,15 +817,10 @@ def eval_batch(elem, order, pts, dofs, verts=None, out=None, stream=None, mappin
     if order < 0:
         raise ValueError("negative derivative order")
     shape = (nreq, num_tables(sd, order), nrhs) + elem.value_shape + (npts,)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        elem.kernel(order, npts, nrhs)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.evallib.fx_eval_batch(ctx.handle, elem.handle, code, int(order), nreq, npts, nrhs, _dev_ptr(pts),
-                                             None if verts is None else _dev_ptr(verts), _dev_ptr(dofs), _dev_ptr(out),
-                                             _stream_ptr(stream)))
+    out = _out_or_new(out, shape, ctx, lambda: elem.kernel(order, npts, nrhs))
+    _lib.companion_check(_lib.evallib.fx_eval_batch(ctx.handle, elem.handle, code, int(order), nreq, npts, nrhs, _dev_ptr(pts),
+                                                     None if verts is None else _dev_ptr(verts), _dev_ptr(dofs), _dev_ptr(out),
+                                                     _stream_ptr(stream)))
     return out
 
 
@@ -838,9 +830,7 @@ TRACE_MODES = {"identify": 0, "facet": 1, "facets": 2}      # include/fiat_amd_t
 def trace_kernel(fd, degree, nfac, npts):
     """Kernel instance, output route and requests per item of a shape (fx_trace_kernel; host only):
     ``"fxk::trace_kernel<fd,degree> image|stream P=<p>"``, degree -1 for the run-time-degree instance."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.tracelib.fx_trace_kernel(int(fd), int(degree), int(nfac), int(npts), buf, len(buf)))
-    return buf.value.decode()
+    return _route(_lib.tracelib.fx_trace_kernel, fd, degree, nfac, npts)
 
 
 def trace_tabulate_batch(fd, degree, nfac, C, mode, pts, facet=0, facets=None, lam0=None, G=None, out=None, stream=None,
@@ -868,13 +858,8 @@ def trace_tabulate_batch(fd, degree, nfac, C, mode, pts, facet=0, facets=None, l
         if lam0.shape != (fd + 2,) or G.shape != (fd + 2, fd + 1):
             raise ValueError("the barycentric map needs lam0 (sd + 1,) and G (sd + 1, sd)")
     shape = (nreq, 1, nfac * nf, npts)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        trace_kernel(fd, degree, nfac, npts)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.tracelib.fx_trace_tabulate_batch(
+    out = _out_or_new(out, shape, ctx, lambda: trace_kernel(fd, degree, nfac, npts))
+    _lib.companion_check(_lib.tracelib.fx_trace_tabulate_batch(
         ctx.handle, int(fd), int(degree), int(nfac), TRACE_MODES[mode], int(facet),
         _dev_ptr(facets) if mode == "facets" else None, _dev_ptr(C),
         host_ptr(lam0) if mode == "identify" else None, host_ptr(G) if mode == "identify" else None,
@@ -894,8 +879,8 @@ class SFormsTable:
             raise ValueError("coef must have shape (nrows, sd) and codes (nrows, sd, sd)")
         self.sd, self.degree, self.nrows = int(sd), int(degree), int(coef.shape[0])
         h = c_void_p()
-        _lib.ser_check(_lib.sflib.fx_sforms_element_create(self.ctx.handle, self.sd, self.degree, self.nrows, host_ptr(coef),
-                                                          host_ptr(codes), ctypes.byref(h)))
+        _lib.companion_check(_lib.sflib.fx_sforms_element_create(
+            self.ctx.handle, self.sd, self.degree, self.nrows, host_ptr(coef), host_ptr(codes), ctypes.byref(h)))
         self.handle = h
 
     def __del__(self):
@@ -911,9 +896,7 @@ class SFormsTable:
 def sforms_kernel(sd, degree, nrows, order, npts):
     """Kernel instance, output route, requests per item and image budget of a shape (fx_sforms_kernel; host only):
     ``"fxk::sforms_kernel<sd,order> image|stream P=<p> budget=<bytes>"``."""
-    buf = ctypes.create_string_buffer(160)
-    _lib.ser_check(_lib.sflib.fx_sforms_kernel(int(sd), int(degree), int(nrows), int(order), int(npts), buf, len(buf)))
-    return buf.value.decode()
+    return _route(_lib.sflib.fx_sforms_kernel, sd, degree, nrows, order, npts)
 
 
 def sforms_tabulate_batch(table, lo, hi, order, pts, out=None, stream=None):
@@ -932,12 +915,8 @@ def sforms_tabulate_batch(table, lo, hi, order, pts, out=None, stream=None):
     if order < 0:
         raise ValueError("negative derivative order")
     shape = (nreq, num_tables(sd, order), table.nrows, sd, npts)
-    if out is None:
-        # (the plan is asked first: a shape without an instance raises before anything is allocated)
-        sforms_kernel(sd, table.degree, table.nrows, order, npts)
-        out = torch.empty(shape, dtype=torch.float64, device=ctx.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != ctx.device:
-        raise ValueError("out has the wrong shape/dtype/layout")
-    _lib.ser_check(_lib.sflib.fx_sforms_tabulate_batch(ctx.handle, table.handle, host_ptr(lo), host_ptr(hi), int(order), nreq, npts,
-                                                      _dev_ptr(pts), _dev_ptr(out), _stream_ptr(stream)))
+    out = _out_or_new(out, shape, ctx, lambda: sforms_kernel(sd, table.degree, table.nrows, order, npts))
+    _lib.companion_check(_lib.sflib.fx_sforms_tabulate_batch(
+        ctx.handle, table.handle, host_ptr(lo), host_ptr(hi), int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out),
+        _stream_ptr(stream)))
     return out
