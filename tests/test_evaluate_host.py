@@ -18,6 +18,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import evaluate_cells_reference as C  # noqa: E402
 import evaluate_reference as R  # noqa: E402
 import make_golden_evaluate as M  # noqa: E402
 
@@ -74,6 +75,40 @@ def test_restatement_drift_from_extended_precision():
             assert e[0] <= STANDING[0] and e[1] <= STANDING[1], (name, physical, e)
 
 
+CELL_CASES = [(c, False) for c in C.ALL_CASES] + [(c, True) for c in C.OWN_CASES]
+
+
+@pytest.mark.parametrize("case,own", CELL_CASES, ids=["-".join(str(x) for x in c) + ("-own" if own else "") for c, own in CELL_CASES])
+def test_restatement_on_cells_against_closed_form(case, own):
+    """Every batch that tests/test_gpu_evaluate_cells.py runs, here in float64 through the restatement against the closed-form
+    oracle (the reference's tables on its reference cell, chained through B^-1 and pushed by J^-T or J / det J), every request
+    compared at the standing 1e-12 / 1e-10: the inputs satisfy the stated conditions (cond_2(B) <= 8, both orientations) and
+    the oracle alone stays inside the tolerances.  Measured (the printed lines are the record, run with -s): at most 1.8e-14 /
+    1.5e-14 on UFC-built elements; 1.9e-13 / 3.6e-13 for elements built on the fixture's skewed cell, where the oracle is the
+    reference's element built on that cell and the figure is the same in extended precision: the reference's own rounding on
+    a cell with edges of 0.05, not the conditioning of the requests' cells."""
+    b = C.batch(*case, own=own)
+    nreq, npts, nrhs = case[3], case[2], case[4]
+    assert b["ref"].shape[:3] == (nreq, len(R.jet(C.meta(case[0])["sd"], case[1])), nrhs) and b["ref"].shape[-1] == npts
+    if nreq > 1:
+        assert not np.array_equal(b["idx"][0], b["idx"][1]) or npts == 1
+    e0, e1 = C.worst(C.restated(case[0], case[1], b, own=own), b["ref"])
+    print(f"{case}{' own' if own else ''}: values {e0:.2e} derivatives {e1:.2e}")
+    assert e0 <= STANDING[0] and e1 <= STANDING[1], (case, e0, e1)
+
+
+def test_cell_case_lists():
+    """The lists reach all 15 instances with per-request cells; the shapes are the ones their names promise."""
+    assert C.instances_with_cells() == {(sd, o, v) for sd in (1, 2, 3) for o in range(3) for v in {1, sd}}
+    assert len(C.FAMILY_CASES) == len(FUSED) == 19
+    assert max(c[3] for c in C.ALL_CASES) <= 200
+    assert C.plan("lag_tri2", 0, 7) == (9, 1) and C.plan("lag_tri2", 1, 70) == (1, 2)        # the alignment shapes
+    assert C.plan("lag_tet3", 2, 23) == (2, 1) and C.plan("rt_tet2", 2, 70) == (1, 2) and C.plan("ned_tri3", 2, 9) == (7, 1)
+    for name in C.SHAPE_ELEMENTS:
+        assert 1 < C.plan(name, 2, 1)[0] < 64                                                 # P set by the LDS budget
+        assert [C.plan(name, 2, p)[1] for p in C.SHAPE_POINTS] == [1, 1, 1, 2, 3]
+
+
 def c_fold(name):
     m = meta(name)
     coeffs = np.ascontiguousarray(G[f"{name}_coeffs"], dtype=np.float64)
@@ -113,13 +148,15 @@ def walk_cases():
                     cell=fo.UFC_SIMPLEX[m["sd"]], coeffs=G[f"{name}_coeffs"].reshape(m["ndof"], m["vdim"], -1), dofs=G[f"{name}_dofs"])
         cases.append(dict(base, mapping=0, verts=None, pts=G[f"{name}_pts"], ref=G[f"{name}_ref"]))
         cases.append(dict(base, mapping=m["mapping"], verts=G[f"{name}_verts"], pts=G[f"{name}_ppts"], ref=G[f"{name}_pref"]))
-    return cases
+    # random cells of both orientations per (sd, vdim, mapping), and elements built on their own skewed cell
+    return cases + C.walk_cell_cases()
 
 
 def test_walk_program_against_fixture(tmp_path):
     """tools/evaluate_walk_host.cpp: the kernel's __host__ __device__ walk, geometry and Piola matrix compiled for the CPU,
-    every instance (sd, order, vdim), on both cells of every fixture case at the standing tolerances (the program's exit
-    status)."""
+    every instance (sd, order, vdim), on both cells of every fixture case, on three random cells (one negatively oriented)
+    per (sd, vdim, mapping) against the closed-form oracle, and per dimension on an element built on its own skewed cell with
+    and without a request's cell on top, at the standing tolerances (the program's exit status)."""
     cxx = shutil.which("g++") or shutil.which("c++")
     if cxx is None:
         pytest.skip("no C++ compiler")
@@ -128,6 +165,9 @@ def test_walk_program_against_fixture(tmp_path):
                     os.path.join(ROOT, "tools", "evaluate_walk_host.cpp"), "-o", str(exe)], check=True, capture_output=True)
     path = tmp_path / "cases.txt"
     cases = walk_cases()
+    assert len(cases) == 2 * 19 + 3 * 7 + 2 * 3
+    assert sum(c["verts"] is not None and np.linalg.det(C.edge_matrices(np.asarray(c["verts"])[None])[0]) < 0 for c in cases) >= 7
+    assert sum(not np.array_equal(c["cell"], fo.UFC_SIMPLEX[c["sd"]]) for c in cases) == 6
     R.write_walk_cases(path, cases)
     run = subprocess.run([str(exe), str(path)], capture_output=True, text=True)
     print(run.stdout[-3000:])
