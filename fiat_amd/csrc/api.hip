@@ -660,6 +660,11 @@ struct Launch {
     int cgrid = 0, clds_bytes = 0;
 };
 
+// Every registry row below is written once, as the template arguments of its row builder: the shape facts the planner
+// reads, the recurrence-table check and the launcher(s) all come from those arguments.
+using LaunchFn = int (*)(const Launch&, hipStream_t);
+using MatchFn = bool (*)(const fx::Program&);
+
 // ---- registry of shape-specialised kernels ----------------------------------------
 // One entry per <SD, N, ORDER, ROWS, NT>; everything else runs the generic kernel.
 constexpr int FIXED_NW = 4;  // 256-thread workgroups: one wave per SIMD, 2 workgroups per CU
@@ -670,24 +675,9 @@ struct FixedShape {
     bool fullimg;    // LDS image of a whole request (false: half of its tables)
     int nw;          // waves per workgroup of the paired kernel (8 = a whole CU; fewer when the images are large)
     bool can_piola;  // an instance with the Piola map applied to the LDS image exists (vector-valued, per-request cells)
+    MatchFn matches;  // table_matches<SD, N>
+    LaunchFn launch;  // launch_fixed<...> of exactly these arguments
 };
-const FixedShape kFixedShapes[] = {
-    {3, 3, 1, 20, 6, false, 2, true, 8, false},  // Lagrange P3 tetrahedron, values + gradient, 21..24 points (the benchmark shape)
-    {3, 3, 1, 20, 5, true, 2, true, 8, false},   // ... 17..20 points
-    {3, 3, 1, 20, 4, true, 2, true, 8, false},   // ... 13..16 points
-    {3, 3, 1, 20, 3, true, 2, true, 8, false},   // ... 9..12 points
-    {3, 3, 1, 20, 8, true, 1, false, 8, false},  // P3 tetrahedron, 25..32 points: one request per wave, half image
-    {3, 3, 1, 20, 10, true, 1, false, 8, false}, // ... 33..40 points
-    {3, 3, 1, 20, 12, true, 1, false, 8, false}, // ... 41..48 points
-    {3, 2, 1, 45, 6, true, 1, false, 8, true},   // RT2 tetrahedron (15 x 3 rows), 21..24 points: one request per wave, half image
-    {3, 4, 1, 35, 6, true, 1, false, 8, false},  // Lagrange P4 tetrahedron, 21..24 points
-    {3, 2, 1, 60, 6, true, 1, false, 4, true},   // N2 tetrahedron (20 x 3 rows), 21..24 points: 22 KB half images, four waves (one per SIMD: 180 accumulator registers)
-    {3, 3, 0, 20, 2, true, 2, true, 8, false},   // Lagrange P3 tetrahedron, values only, 17..32 points (45 % on the stacked kernel -> 56 %)
-    {3, 3, 0, 20, 3, true, 1, true, 8, false},   // ... 33..48 points (40 -> 54-58 %; <= 16 points: the stacked kernel is faster)
-    {3, 4, 0, 35, 2, true, 2, true, 8, false},   // Lagrange P4 tetrahedron, values only, 17..32 points (even point counts: 35 rows)
-    {3, 4, 0, 35, 3, true, 1, true, 8, false},   // ... 33..48 points (the 44-point degree-8 rule: 31 -> 46 %)
-};
-
 template <int SD, int N>
 bool table_matches(const fx::Program& P) {
     constexpr fxk::StepTable<SD, N> T{};
@@ -864,6 +854,29 @@ int launch_fixed(const Launch& L, hipStream_t s) {
     }
 }
 
+template <int SD, int N, int ORDER, int ROWS, int NT, bool PAIR_ONLY = false, int RPW = 2, bool FULLIMG = true, int PAIR_NW = 8,
+          bool CAN_PIOLA = false>
+constexpr FixedShape fixed_row() {
+    return {SD, N, ORDER, ROWS, NT, PAIR_ONLY, RPW, FULLIMG, PAIR_NW, CAN_PIOLA, &table_matches<SD, N>,
+            &launch_fixed<SD, N, ORDER, ROWS, NT, PAIR_ONLY, RPW, FULLIMG, PAIR_NW, CAN_PIOLA>};
+}
+constexpr FixedShape kFixedShapes[] = {
+    fixed_row<3, 3, 1, 20, 6>(),                           // Lagrange P3 tetrahedron, values + gradient, 21..24 points (the benchmark shape)
+    fixed_row<3, 3, 1, 20, 5, true>(),                     // ... 17..20 points
+    fixed_row<3, 3, 1, 20, 4, true>(),                     // ... 13..16 points
+    fixed_row<3, 3, 1, 20, 3, true>(),                     // ... 9..12 points
+    fixed_row<3, 3, 1, 20, 8, true, 1, false>(),           // P3 tetrahedron, 25..32 points: one request per wave, half image
+    fixed_row<3, 3, 1, 20, 10, true, 1, false>(),          // ... 33..40 points
+    fixed_row<3, 3, 1, 20, 12, true, 1, false>(),          // ... 41..48 points
+    fixed_row<3, 2, 1, 45, 6, true, 1, false, 8, true>(),  // RT2 tetrahedron (15 x 3 rows), 21..24 points: one request per wave, half image
+    fixed_row<3, 4, 1, 35, 6, true, 1, false>(),           // Lagrange P4 tetrahedron, 21..24 points
+    fixed_row<3, 2, 1, 60, 6, true, 1, false, 4, true>(),  // N2 tetrahedron (20 x 3 rows), 21..24 points: 22 KB half images, four waves (one per SIMD: 180 accumulator registers)
+    fixed_row<3, 3, 0, 20, 2, true>(),                     // Lagrange P3 tetrahedron, values only, 17..32 points (45 % on the stacked kernel -> 56 %)
+    fixed_row<3, 3, 0, 20, 3, true, 1>(),                  // ... 33..48 points (40 -> 54-58 %; <= 16 points: the stacked kernel is faster)
+    fixed_row<3, 4, 0, 35, 2, true>(),                     // Lagrange P4 tetrahedron, values only, 17..32 points (even point counts: 35 rows)
+    fixed_row<3, 4, 0, 35, 3, true, 1>(),                  // ... 33..48 points (the 44-point degree-8 rule: 31 -> 46 %)
+};
+
 // ---- registry of the stacked-matrix kernel: <SD, N, CT, G> ----------------------------------
 // (sd, n) of the expansion set, CT column tiles per group of G requests: npts <= 16 CT / G
 struct StackedShape {
@@ -875,91 +888,14 @@ struct StackedShape {
               // -6: per-request cells, order 0, Piola map of a vector-valued element applied in the kernel
               // -1: point-chunked instance (a unit = 16 ct points of one request): any number of points >= 13, odd
               //      table sizes too -- taken when no whole-request instance applies
+              // -7: request-per-workgroup kernel (simplex_wg.hpp)
+    MatchFn matches;  // table_matches<SD, N>
+    // The compiled twins of the row, nullptr where none is compiled (stacked_row below): `base`; `odd`, the 8-byte flush for
+    // tables of an odd number of doubles; `pio` / `pio_odd`, the same two with the Piola map on the accumulators; `lo`, two
+    // waves per SIMD for orders <= 1.  run_stacked prefers pio, then odd, then lo.
+    LaunchFn base, odd, pio, pio_odd, lo;
+    bool mixr;  // the base twin mixes on the accumulators (the other chain-rule twins always do): sizes LDS
 };
-const StackedShape kStackedShapes[] = {
-    {3, 3, 3, 2, 5},  // Lagrange P3 tetrahedron, values + gradient (80 stacked rows): the benchmark shape C2, 17..24 points
-    {3, 3, 2, 1, 5},  // ... 25..32 points
-    {3, 3, 3, 1, 5},  // ... 33..48 points
-    // rtc -2: per-request cells, order 1 (tetrahedra and triangles), chain rule applied inside the kernel (simplex_stacked.hpp MIXT;
-    // FIAT_AMD_STACKED_MIX=0 switches them off: whole-request instances + table_mix_kernel).  Degree 6 with three
-    // column tiles is not registered: 150+ spilled registers make it slower than the two-pass route.
-    {3, 6, 2, 1, -2}, {3, 5, 3, 2, -2}, {3, 5, 2, 1, -2}, {3, 5, 3, 1, -2},
-    {2, 6, 3, 2, -2}, {2, 6, 2, 1, -2}, {2, 6, 3, 1, -2}, {2, 5, 3, 2, -2}, {2, 5, 2, 1, -2}, {2, 5, 3, 1, -2},
-    {3, 4, 3, 2, -2}, {3, 4, 2, 1, -2}, {3, 4, 3, 1, -2}, {3, 3, 3, 2, -2}, {3, 3, 2, 1, -2}, {3, 3, 3, 1, -2},
-    {3, 6, 3, 2, 0},  // degree-6 tetrahedron (DG P6 with Hessians: C4), 17..24 points
-    {3, 6, 2, 1, 0},  // ... 25..32 points
-    {3, 6, 3, 1, 0},  // ... 33..48 points
-    {3, 5, 3, 2, 0},  // degree-5 tetrahedron
-    {3, 5, 2, 1, 0},
-    {3, 5, 3, 1, 0},
-    {3, 4, 3, 2, 0},  // degree-4 tetrahedron (with Hessians: 350 stacked rows)
-    {3, 4, 2, 1, 0},
-    {3, 4, 3, 1, 0},
-    {3, 3, 3, 2, 0},  // degree-3 tetrahedron (vector-valued elements, Hessians of P3)
-    {3, 3, 2, 1, 0},
-    {3, 3, 3, 1, 0},
-    {2, 6, 3, 2, 0},  // degree-5 / 6 triangles
-    {2, 6, 2, 1, 0},
-    {2, 6, 3, 1, 0},
-    {2, 5, 3, 2, 0},
-    {2, 5, 2, 1, 0},
-    {2, 5, 3, 1, 0},
-    {3, 6, 3, 3, 0},                   // 13..16 points ((3, 6, 4, 1) would spill 62 registers: 49..64 points are point-chunked)
-    // 13..16 and 49..64 points
-    {3, 5, 3, 3, 0}, {3, 5, 4, 1, 0},
-    {3, 4, 3, 3, 0}, {3, 4, 4, 1, 0},
-    {3, 3, 3, 3, 0}, {3, 3, 4, 1, 0},
-    {2, 6, 3, 3, 0}, {2, 6, 4, 1, 0},
-    {2, 5, 3, 3, 0}, {2, 5, 4, 1, 0},
-    {3, 2, 3, 2, 0}, {3, 2, 2, 1, 0}, {3, 2, 3, 1, 0}, {3, 2, 3, 3, 0}, {3, 2, 4, 1, 0},  // degree-2 tetrahedron (N2, RT2, BDM2 ...)
-    {3, 6, 3, 1, -1}, {3, 5, 3, 1, -1}, {3, 4, 3, 1, -1}, {3, 3, 3, 1, -1}, {3, 2, 3, 1, -1}, {2, 6, 3, 1, -1}, {2, 5, 3, 1, -1},  // point-chunked
-    // round 2 (tools/coverage_map.py): the quadrature sizes of the mid-degree vector-valued elements that were left to the
-    // lane-local / generic kernels at 8-30 % of the HBM peak
-    {3, 2, 3, 4, 0},                                   // degree-2 tetrahedron, 9..12 points (the 11-point degree-4 rule)
-    {2, 4, 3, 3, 0}, {2, 4, 3, 2, 0}, {2, 4, 2, 1, 0}, {2, 4, 3, 1, 0},  // degree-4 triangle (N4 / RT4 / BDM3 ...): 13..16, 17..24, 25..32, 33..48 points
-    {2, 3, 3, 4, 0}, {2, 3, 3, 3, 0}, {2, 3, 3, 2, 0}, {2, 3, 2, 1, 0},  // degree-3 triangle: 9..12, 13..16, 17..24, 25..32 points
-    {3, 2, 3, 6, 0}, {3, 2, 3, 8, 0}, {3, 2, 3, 12, 0},                  // few points: 7..8, 5..6, <= 4 (six / eight / twelve requests per group)
-    {2, 3, 3, 6, 0}, {2, 3, 3, 8, 0}, {2, 4, 3, 4, 0}, {2, 4, 3, 6, 0},
-    {2, 4, 3, 1, -1}, {2, 3, 3, 1, -1},                                  // point-chunked: odd table sizes, more points
-    // per-request cells, values + gradient, chain rule inside the kernel (as the rtc -2 block above)
-    {3, 2, 3, 4, -2}, {3, 2, 3, 3, -2}, {3, 2, 3, 2, -2}, {3, 2, 2, 1, -2},
-    {2, 3, 3, 4, -2}, {2, 3, 3, 3, -2}, {2, 3, 3, 2, -2}, {2, 4, 3, 3, -2}, {2, 4, 3, 2, -2}, {2, 4, 2, 1, -2},
-    // round 3: expansion degrees 7 and 8 (were on the generic kernel at 11-30 % of the HBM peak).  Tetrahedra of degree 7 hold
-    // 30 K-steps x 2 column tiles of B fragments (60 doubles per lane, as degree 6 with three tiles); their quadrature rules
-    // have hundreds of points, so the point-chunked instance (32 points a unit) is the one that matters
-    {3, 7, 2, 1, 0}, {3, 7, 2, 1, -1},
-    {2, 7, 3, 1, 0}, {2, 7, 2, 1, 0}, {2, 7, 3, 1, -1}, {2, 8, 4, 1, 0}, {2, 8, 3, 1, -1},
-    // round 3: per-request cells with Hessians, chain rule on the accumulators (rtc -3; were two passes: kernel + table_mix_kernel)
-    {3, 2, 3, 4, -3}, {3, 2, 3, 3, -3}, {3, 2, 3, 2, -3}, {3, 2, 2, 1, -3},
-    {3, 3, 3, 2, -3}, {3, 3, 2, 1, -3}, {3, 3, 3, 1, -3},
-    {3, 4, 3, 2, -3}, {3, 4, 2, 1, -3}, {3, 4, 3, 1, -3},
-    {3, 5, 2, 1, -3}, {3, 6, 2, 1, -3},
-    {2, 3, 3, 4, -3}, {2, 3, 3, 3, -3}, {2, 3, 3, 2, -3},
-    {2, 4, 3, 3, -3}, {2, 4, 3, 2, -3}, {2, 4, 2, 1, -3},
-    {2, 5, 3, 2, -3}, {2, 5, 2, 1, -3}, {2, 5, 3, 1, -3},
-    {2, 6, 3, 2, -3}, {2, 6, 2, 1, -3}, {2, 6, 3, 1, -3},
-    // degree-6 tetrahedra with three column tiles, order 1 with cells: accumulator-side mixing needs ~150 registers fewer than
-    // the flush-side version that could not be registered (see the rtc -2 block above): 0 scratch
-    {3, 6, 3, 2, -2}, {3, 6, 3, 1, -2},
-    // point-chunked units with the chain rule inside the kernel: order 1 (rtc -4), order 2 (rtc -5) -- rules of more points than a
-    // whole-request instance holds (the 74- and 122-point rules of P5 / P6 tetrahedra ...), any table size
-    {3, 6, 3, 1, -4}, {3, 5, 3, 1, -4}, {3, 4, 3, 1, -4}, {3, 3, 3, 1, -4}, {3, 2, 3, 1, -4}, {2, 6, 3, 1, -4}, {2, 5, 3, 1, -4},
-    {3, 6, 2, 1, -5}, {3, 5, 2, 1, -5}, {3, 4, 2, 1, -5}, {3, 3, 3, 1, -5}, {3, 2, 3, 1, -5}, {2, 6, 3, 1, -5}, {2, 5, 3, 1, -5},
-    // vector-valued elements on per-request cells with their Piola map, values only (rtc -6): the map is applied to the
-    // accumulators (simplex_stacked.hpp PIO; with derivatives: the PIO twins of the rtc -2 / -3 instances of these shapes)
-    {3, 2, 3, 4, -6}, {3, 2, 3, 3, -6}, {3, 2, 3, 2, -6}, {3, 2, 2, 1, -6}, {3, 3, 3, 2, -6}, {3, 3, 2, 1, -6}, {3, 3, 3, 1, -6},
-    {2, 3, 3, 4, -6}, {2, 3, 3, 3, -6}, {2, 3, 3, 2, -6}, {2, 4, 3, 3, -6}, {2, 4, 3, 2, -6}, {2, 4, 2, 1, -6},
-    // point chunks of two column tiles: rules whose 32-point chunks need fewer column tiles than their 48-point chunks
-    // (49..64 points: 4 against 6; 97..128 points -- the 122-point rule of degree 6 -- 8 against 9)
-    {3, 6, 2, 1, -1}, {3, 5, 2, 1, -1},
-    {3, 6, 2, 1, -4}, {3, 5, 2, 1, -4},  // ... with the order-1 chain rule of per-request cells inside
-    // round 4, rtc -7: the request-per-workgroup kernel (simplex_wg.hpp, its own translation unit wg.hip) -- rules of 49..128
-    // points, expansion values of the whole request in LDS, a row tile leaves as 16 x npts contiguous doubles; ct = the most
-    // column tiles an instance has (the launch takes ceil(npts / 16)).  Visited before the point-chunked instances.
-    {3, 6, 8, 1, -7}, {3, 5, 8, 1, -7}, {3, 4, 8, 1, -7}, {3, 3, 8, 1, -7}, {2, 6, 8, 1, -7}, {2, 5, 8, 1, -7},
-};
-// shapes whose in-kernel chain-rule instances (rtc -2 / -3 / -6) have a twin that applies the Piola map too
-constexpr bool stacked_has_pio(int sd, int n) { return (sd == 3 && (n == 2 || n == 3)) || (sd == 2 && (n == 3 || n == 4)); }
 constexpr int STACKED_NW = 4;  // one wave per SIMD
 // Order-1 in-kernel chain rule (rtc -2): on the accumulators (MIXR) or in the flush.  tools/mixr_ab.sh, all 26 instances, ABAB:
 // accumulator-side 0.84-1.00 of the flush-side launch time except on four single-request triangle instances (1.01-1.05); of
@@ -1069,6 +1005,142 @@ int launch_stacked(const Launch& L, hipStream_t s) {
     return FX_OK;
 }
 
+int launch_wg(const Launch& L, hipStream_t s);  // (rtc -7; defined below the table it reads)
+
+// ---- rows of the stacked registry -------------------------------------------------------------
+// A row is its template arguments <SD, N, CT, G>, its kind (StackedShape::rtc) and the twins compiled beside its base
+// instance.  MIXT (tables the kernel mixes), CHUNK, MIXR and WPS of every twin follow from kind and sd here and nowhere else.
+enum : unsigned { TW_ODD = 1, TW_PIO = 2, TW_PIO_ODD = 4, TW_LO = 8 };
+constexpr int stacked_mixt(int sd, int rtc) {
+    return (rtc == -2 || rtc == -4) ? 1 + sd : (rtc == -3 || rtc == -5) ? 1 + sd + sd * (sd + 1) / 2 : rtc == -6 ? 1 : 0;
+}
+// accumulator-side mixing of the base twin: orders 2 and the chunked units always, order 1 by mixr1() -- except degree-6
+// tetrahedra on three column tiles, which exist accumulator-side only (the flush-side version spills 150+ registers)
+constexpr bool stacked_mixr(int sd, int n, int ct, int g, int rtc) {
+    return rtc == -2 ? ((sd == 3 && n == 6 && ct == 3) || mixr1(sd, n, ct, g)) : rtc <= -3 && rtc >= -6;
+}
+// (WPS = 2 variants: instances a few registers above 256 recompiled for two waves per SIMD -- values and gradients have short
+// row sweeps, the second wave covers a group's production phase: P6 triangles 27-35 -> 32-43 %, P4 tetrahedra at 13-24
+// points 28-45 -> 32-50 %; with Hessians the sweep is MFMA-bound and one 512-register wave is faster, tools/wps_probe.py)
+template <int SD, int N, int CT, int G, int RTC, unsigned TW = 0>
+constexpr StackedShape stacked_row() {
+    constexpr int MIXT = stacked_mixt(SD, RTC);
+    constexpr bool CHUNK = RTC == -1 || RTC == -4 || RTC == -5;
+    constexpr bool MIXR = stacked_mixr(SD, N, CT, G, RTC);
+    constexpr int WPS = (RTC == -2 || RTC == -3) && SD == 2 ? mixr_wps(SD, N) : 1;  // of the base twin; the others run one wave per SIMD, `lo` two
+    static_assert(!(TW & TW_LO) || RTC == 0 || RTC == -1, "two waves per SIMD: a twin of the instances without a chain rule");
+    static_assert(!(TW & (TW_PIO | TW_PIO_ODD)) || RTC == -2 || RTC == -3 || RTC == -6, "Piola twins: whole requests with the chain rule inside");
+    StackedShape r{SD, N, CT, G, RTC, &table_matches<SD, N>, nullptr, nullptr, nullptr, nullptr, nullptr, MIXR};
+    if constexpr (RTC > 0) r.base = &launch_stacked<SD, N, CT, G, RTC, 3>;
+    else if constexpr (RTC == -7) r.base = &launch_wg;
+    else if constexpr (RTC != -6) r.base = &launch_stacked<SD, N, CT, G, 0, WPS, CHUNK, MIXT, false, MIXR>;  // (-6: nothing but the map to mix, no base)
+    if constexpr ((TW & TW_ODD) != 0) r.odd = &launch_stacked<SD, N, CT, G, 0, 1, CHUNK, MIXT, true, MIXT != 0>;
+    if constexpr ((TW & TW_PIO) != 0) r.pio = &launch_stacked<SD, N, CT, G, 0, 1, CHUNK, MIXT, false, true, 1>;
+    if constexpr ((TW & TW_PIO_ODD) != 0) r.pio_odd = &launch_stacked<SD, N, CT, G, 0, 1, CHUNK, MIXT, true, true, 1>;
+    if constexpr ((TW & TW_LO) != 0) r.lo = &launch_stacked<SD, N, CT, G, 0, 2, CHUNK>;
+    return r;
+}
+// one builder per kind, named after it
+template <int SD, int N, int CT, int G, int RTC> constexpr StackedShape resident() { static_assert(RTC > 0, "row tiles"); return stacked_row<SD, N, CT, G, RTC>(); }
+template <int SD, int N, int CT, int G, unsigned TW = 0> constexpr StackedShape whole() { return stacked_row<SD, N, CT, G, 0, TW>(); }
+template <int SD, int N, int CT, int G, unsigned TW = 0> constexpr StackedShape chunk() { return stacked_row<SD, N, CT, G, -1, TW>(); }
+template <int SD, int N, int CT, int G, unsigned TW = 0> constexpr StackedShape mix1() { return stacked_row<SD, N, CT, G, -2, TW>(); }
+template <int SD, int N, int CT, int G, unsigned TW = 0> constexpr StackedShape mix2() { return stacked_row<SD, N, CT, G, -3, TW>(); }
+template <int SD, int N, int CT, int G> constexpr StackedShape chunk_mix1() { return stacked_row<SD, N, CT, G, -4>(); }
+template <int SD, int N, int CT, int G> constexpr StackedShape chunk_mix2() { return stacked_row<SD, N, CT, G, -5>(); }
+template <int SD, int N, int CT, int G, unsigned TW = 0> constexpr StackedShape piola() { return stacked_row<SD, N, CT, G, -6, TW | TW_PIO>(); }
+template <int SD, int N, int CT, int G> constexpr StackedShape wg() { return stacked_row<SD, N, CT, G, -7>(); }
+
+constexpr StackedShape kStackedShapes[] = {
+    resident<3, 3, 3, 2, 5>(),  // Lagrange P3 tetrahedron, values + gradient (80 stacked rows): the benchmark shape C2, 17..24 points
+    resident<3, 3, 2, 1, 5>(),  // ... 25..32 points
+    resident<3, 3, 3, 1, 5>(),  // ... 33..48 points
+    // rtc -2: per-request cells, order 1 (tetrahedra and triangles), chain rule applied inside the kernel (simplex_stacked.hpp MIXT;
+    // FIAT_AMD_STACKED_MIX=0 switches them off: whole-request instances + table_mix_kernel).  Degree 6 with three
+    // column tiles: flush-side mixing spills 150+ registers; the accumulator-side rows are further down.
+    mix1<3, 6, 2, 1>(), mix1<3, 5, 3, 2>(), mix1<3, 5, 2, 1>(), mix1<3, 5, 3, 1>(),
+    mix1<2, 6, 3, 2>(), mix1<2, 6, 2, 1>(), mix1<2, 6, 3, 1>(), mix1<2, 5, 3, 2>(), mix1<2, 5, 2, 1, TW_ODD>(), mix1<2, 5, 3, 1, TW_ODD>(),
+    mix1<3, 4, 3, 2, TW_ODD>(), mix1<3, 4, 2, 1>(), mix1<3, 4, 3, 1>(), mix1<3, 3, 3, 2, TW_ODD | TW_PIO | TW_PIO_ODD>(), mix1<3, 3, 2, 1, TW_PIO>(), mix1<3, 3, 3, 1, TW_PIO>(),
+    whole<3, 6, 3, 2>(),  // degree-6 tetrahedron (DG P6 with Hessians: C4), 17..24 points
+    whole<3, 6, 2, 1>(),  // ... 25..32 points
+    whole<3, 6, 3, 1>(),  // ... 33..48 points
+    whole<3, 5, 3, 2>(),  // degree-5 tetrahedron
+    whole<3, 5, 2, 1>(),
+    whole<3, 5, 3, 1>(),
+    whole<3, 4, 3, 2, TW_ODD | TW_LO>(),  // degree-4 tetrahedron (with Hessians: 350 stacked rows)
+    whole<3, 4, 2, 1>(),
+    whole<3, 4, 3, 1>(),
+    whole<3, 3, 3, 2, TW_ODD>(),  // degree-3 tetrahedron (vector-valued elements, Hessians of P3)
+    whole<3, 3, 2, 1>(),
+    whole<3, 3, 3, 1>(),
+    whole<2, 6, 3, 2, TW_LO>(),  // degree-5 / 6 triangles
+    whole<2, 6, 2, 1, TW_LO>(),
+    whole<2, 6, 3, 1, TW_LO>(),
+    whole<2, 5, 3, 2, TW_LO>(),
+    whole<2, 5, 2, 1, TW_ODD | TW_LO>(),
+    whole<2, 5, 3, 1, TW_LO>(),
+    whole<3, 6, 3, 3>(),  // 13..16 points ((3, 6, 4, 1) would spill 62 registers: 49..64 points are point-chunked)
+    // 13..16 and 49..64 points
+    whole<3, 5, 3, 3>(), whole<3, 5, 4, 1>(),
+    whole<3, 4, 3, 3, TW_LO>(), whole<3, 4, 4, 1>(),
+    whole<3, 3, 3, 3>(), whole<3, 3, 4, 1>(),
+    whole<2, 6, 3, 3>(), whole<2, 6, 4, 1>(),
+    whole<2, 5, 3, 3>(), whole<2, 5, 4, 1>(),
+    whole<3, 2, 3, 2, TW_ODD>(), whole<3, 2, 2, 1>(), whole<3, 2, 3, 1>(), whole<3, 2, 3, 3>(), whole<3, 2, 4, 1>(),  // degree-2 tetrahedron (N2, RT2, BDM2 ...)
+    chunk<3, 6, 3, 1>(), chunk<3, 5, 3, 1>(), chunk<3, 4, 3, 1>(), chunk<3, 3, 3, 1>(), chunk<3, 2, 3, 1>(), chunk<2, 6, 3, 1, TW_LO>(), chunk<2, 5, 3, 1, TW_LO>(),  // point-chunked
+    // round 2 (tools/coverage_map.py): the quadrature sizes of the mid-degree vector-valued elements that were left to the
+    // lane-local / generic kernels at 8-30 % of the HBM peak
+    whole<3, 2, 3, 4, TW_ODD>(),  // degree-2 tetrahedron, 9..12 points (the 11-point degree-4 rule)
+    whole<2, 4, 3, 3>(), whole<2, 4, 3, 2>(), whole<2, 4, 2, 1>(), whole<2, 4, 3, 1>(),  // degree-4 triangle (N4 / RT4 / BDM3 ...): 13..16, 17..24, 25..32, 33..48 points
+    whole<2, 3, 3, 4>(), whole<2, 3, 3, 3>(), whole<2, 3, 3, 2>(), whole<2, 3, 2, 1>(),  // degree-3 triangle: 9..12, 13..16, 17..24, 25..32 points
+    whole<3, 2, 3, 6>(), whole<3, 2, 3, 8>(), whole<3, 2, 3, 12>(),  // few points: 7..8, 5..6, <= 4 (six / eight / twelve requests per group)
+    whole<2, 3, 3, 6>(), whole<2, 3, 3, 8>(), whole<2, 4, 3, 4>(), whole<2, 4, 3, 6>(),
+    chunk<2, 4, 3, 1>(), chunk<2, 3, 3, 1>(),  // point-chunked: odd table sizes, more points
+    // per-request cells, values + gradient, chain rule inside the kernel (as the rtc -2 block above)
+    mix1<3, 2, 3, 4, TW_PIO | TW_PIO_ODD>(), mix1<3, 2, 3, 3, TW_PIO>(), mix1<3, 2, 3, 2, TW_PIO>(), mix1<3, 2, 2, 1, TW_PIO>(),
+    mix1<2, 3, 3, 4, TW_PIO>(), mix1<2, 3, 3, 3, TW_PIO>(), mix1<2, 3, 3, 2, TW_PIO>(), mix1<2, 4, 3, 3, TW_PIO>(), mix1<2, 4, 3, 2, TW_PIO>(), mix1<2, 4, 2, 1, TW_ODD | TW_PIO>(),
+    // round 3: expansion degrees 7 and 8 (were on the generic kernel at 11-30 % of the HBM peak).  Tetrahedra of degree 7 hold
+    // 30 K-steps x 2 column tiles of B fragments (60 doubles per lane, as degree 6 with three tiles); their quadrature rules
+    // have hundreds of points, so the point-chunked instance (32 points a unit) is the one that matters
+    whole<3, 7, 2, 1>(), chunk<3, 7, 2, 1>(),
+    whole<2, 7, 3, 1>(), whole<2, 7, 2, 1>(), chunk<2, 7, 3, 1>(), whole<2, 8, 4, 1>(), chunk<2, 8, 3, 1>(),
+    // round 3: per-request cells with Hessians, chain rule on the accumulators (rtc -3; were two passes: kernel + table_mix_kernel)
+    mix2<3, 2, 3, 4, TW_ODD | TW_PIO | TW_PIO_ODD>(), mix2<3, 2, 3, 3, TW_PIO>(), mix2<3, 2, 3, 2, TW_PIO>(), mix2<3, 2, 2, 1, TW_PIO>(),
+    mix2<3, 3, 3, 2, TW_ODD | TW_PIO | TW_PIO_ODD>(), mix2<3, 3, 2, 1, TW_PIO>(), mix2<3, 3, 3, 1, TW_PIO>(),
+    mix2<3, 4, 3, 2, TW_ODD>(), mix2<3, 4, 2, 1>(), mix2<3, 4, 3, 1>(),
+    mix2<3, 5, 2, 1>(), mix2<3, 6, 2, 1>(),
+    mix2<2, 3, 3, 4, TW_PIO>(), mix2<2, 3, 3, 3, TW_PIO>(), mix2<2, 3, 3, 2, TW_PIO>(),
+    mix2<2, 4, 3, 3, TW_PIO>(), mix2<2, 4, 3, 2, TW_PIO>(), mix2<2, 4, 2, 1, TW_ODD | TW_PIO>(),
+    mix2<2, 5, 3, 2>(), mix2<2, 5, 2, 1, TW_ODD>(), mix2<2, 5, 3, 1, TW_ODD>(),
+    mix2<2, 6, 3, 2>(), mix2<2, 6, 2, 1>(), mix2<2, 6, 3, 1>(),
+    // degree-6 tetrahedra with three column tiles, order 1 with cells: accumulator-side mixing needs ~150 registers fewer than
+    // the flush-side version that could not be registered (see the rtc -2 block above): 0 scratch
+    mix1<3, 6, 3, 2>(), mix1<3, 6, 3, 1>(),
+    // point-chunked units with the chain rule inside the kernel: order 1 (rtc -4), order 2 (rtc -5) -- rules of more points than a
+    // whole-request instance holds (the 74- and 122-point rules of P5 / P6 tetrahedra ...), any table size
+    chunk_mix1<3, 6, 3, 1>(), chunk_mix1<3, 5, 3, 1>(), chunk_mix1<3, 4, 3, 1>(), chunk_mix1<3, 3, 3, 1>(), chunk_mix1<3, 2, 3, 1>(), chunk_mix1<2, 6, 3, 1>(), chunk_mix1<2, 5, 3, 1>(),
+    chunk_mix2<3, 6, 2, 1>(), chunk_mix2<3, 5, 2, 1>(), chunk_mix2<3, 4, 2, 1>(), chunk_mix2<3, 3, 3, 1>(), chunk_mix2<3, 2, 3, 1>(), chunk_mix2<2, 6, 3, 1>(), chunk_mix2<2, 5, 3, 1>(),
+    // vector-valued elements on per-request cells with their Piola map, values only (rtc -6): the map is applied to the
+    // accumulators (simplex_stacked.hpp PIO; with derivatives: the PIO twins of the rtc -2 / -3 instances of these shapes)
+    piola<3, 2, 3, 4, TW_PIO_ODD>(), piola<3, 2, 3, 3>(), piola<3, 2, 3, 2>(), piola<3, 2, 2, 1>(), piola<3, 3, 3, 2, TW_PIO_ODD>(), piola<3, 3, 2, 1>(), piola<3, 3, 3, 1>(),
+    piola<2, 3, 3, 4>(), piola<2, 3, 3, 3>(), piola<2, 3, 3, 2>(), piola<2, 4, 3, 3>(), piola<2, 4, 3, 2>(), piola<2, 4, 2, 1>(),
+    // point chunks of two column tiles: rules whose 32-point chunks need fewer column tiles than their 48-point chunks
+    // (49..64 points: 4 against 6; 97..128 points -- the 122-point rule of degree 6 -- 8 against 9)
+    chunk<3, 6, 2, 1>(), chunk<3, 5, 2, 1>(),
+    chunk_mix1<3, 6, 2, 1>(), chunk_mix1<3, 5, 2, 1>(),  // ... with the order-1 chain rule of per-request cells inside
+    // round 4, rtc -7: the request-per-workgroup kernel (simplex_wg.hpp, its own translation unit wg.hip) -- rules of 49..128
+    // points, expansion values of the whole request in LDS, a row tile leaves as 16 x npts contiguous doubles; ct = the most
+    // column tiles an instance has (the launch takes ceil(npts / 16)).  Visited before the point-chunked instances.
+    wg<3, 6, 8, 1>(), wg<3, 5, 8, 1>(), wg<3, 4, 8, 1>(), wg<3, 3, 8, 1>(), wg<2, 6, 8, 1>(), wg<2, 5, 8, 1>(),
+};
+constexpr int NSTACKED = (int)(sizeof(kStackedShapes) / sizeof(kStackedShapes[0]));
+constexpr bool stacked_table_ok() {
+    for (const StackedShape& k : kStackedShapes)
+        if ((!k.base && k.rtc != -6) || (k.pio_odd && !k.pio) || (k.rtc == -6 && !k.pio) || !k.matches) return false;
+    return true;
+}
+static_assert(stacked_table_ok(), "every stacked row has a base launcher unless its kind has none, and pio + odd implies pio");
+
 // the request-per-workgroup kernel (rtc -7; simplex_wg.hpp, compiled in wg.hip)
 int launch_wg(const Launch& L, hipStream_t s) {
     const StackedShape& k = kStackedShapes[L.stacked_id];
@@ -1084,166 +1156,12 @@ int launch_wg(const Launch& L, hipStream_t s) {
 }
 
 int run_stacked(const Launch& L, hipStream_t s) {
-    // (WPS = 2 variants: instances a few registers above 256 recompiled for two waves per SIMD -- values and gradients have short
-    // row sweeps, the second wave covers a group's production phase: P6 triangles 27-35 -> 32-43 %, P4 tetrahedra at 13-24
-    // points 28-45 -> 32-50 %; with Hessians the sweep is MFMA-bound and one 512-register wave is faster, tools/wps_probe.py)
-    if (L.stacked_id >= 0 && L.stacked_id < (int)(sizeof(kStackedShapes) / sizeof(kStackedShapes[0])) && kStackedShapes[L.stacked_id].rtc == -7)
-        return launch_wg(L, s);
-    switch (L.stacked_id) {  // (same order as kStackedShapes)
-        case 0: return launch_stacked<3, 3, 3, 2, 5, 3>(L, s);
-        case 1: return launch_stacked<3, 3, 2, 1, 5, 3>(L, s);
-        case 2: return launch_stacked<3, 3, 3, 1, 5, 3>(L, s);
-        case 3: return launch_stacked<3, 6, 2, 1, 0, 1, false, 4, false, mixr1(3, 6, 2, 1)>(L, s);
-        case 4: return launch_stacked<3, 5, 3, 2, 0, 1, false, 4, false, mixr1(3, 5, 3, 2)>(L, s);
-        case 5: return launch_stacked<3, 5, 2, 1, 0, 1, false, 4, false, mixr1(3, 5, 2, 1)>(L, s);
-        case 6: return launch_stacked<3, 5, 3, 1, 0, 1, false, 4, false, mixr1(3, 5, 3, 1)>(L, s);
-        case 7: return launch_stacked<2, 6, 3, 2, 0, mixr_wps(2, 6), false, 3, false, mixr1(2, 6, 3, 2)>(L, s);
-        case 8: return launch_stacked<2, 6, 2, 1, 0, mixr_wps(2, 6), false, 3, false, mixr1(2, 6, 2, 1)>(L, s);
-        case 9: return launch_stacked<2, 6, 3, 1, 0, mixr_wps(2, 6), false, 3, false, mixr1(2, 6, 3, 1)>(L, s);
-        case 10: return launch_stacked<2, 5, 3, 2, 0, mixr_wps(2, 5), false, 3, false, mixr1(2, 5, 3, 2)>(L, s);
-        case 11: return L.kodd ? launch_stacked<2, 5, 2, 1, 0, 1, false, 3, true, true>(L, s) : launch_stacked<2, 5, 2, 1, 0, mixr_wps(2, 5), false, 3, false, mixr1(2, 5, 2, 1)>(L, s);
-        case 12: return L.kodd ? launch_stacked<2, 5, 3, 1, 0, 1, false, 3, true, true>(L, s) : launch_stacked<2, 5, 3, 1, 0, mixr_wps(2, 5), false, 3, false, mixr1(2, 5, 3, 1)>(L, s);
-        case 13: return L.kodd ? launch_stacked<3, 4, 3, 2, 0, 1, false, 4, true, true>(L, s) : launch_stacked<3, 4, 3, 2, 0, 1, false, 4, false, mixr1(3, 4, 3, 2)>(L, s);
-        case 14: return launch_stacked<3, 4, 2, 1, 0, 1, false, 4, false, mixr1(3, 4, 2, 1)>(L, s);
-        case 15: return launch_stacked<3, 4, 3, 1, 0, 1, false, 4, false, mixr1(3, 4, 3, 1)>(L, s);
-        case 16: return L.kpiola ? (L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 4, true, true, 1>(L, s) : launch_stacked<3, 3, 3, 2, 0, 1, false, 4, false, true, 1>(L, s)) : L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 4, true, true>(L, s) : launch_stacked<3, 3, 3, 2, 0, 1, false, 4, false, mixr1(3, 3, 3, 2)>(L, s);
-        case 17: return L.kpiola ? launch_stacked<3, 3, 2, 1, 0, 1, false, 4, false, true, 1>(L, s) : launch_stacked<3, 3, 2, 1, 0, 1, false, 4, false, mixr1(3, 3, 2, 1)>(L, s);
-        case 18: return L.kpiola ? launch_stacked<3, 3, 3, 1, 0, 1, false, 4, false, true, 1>(L, s) : launch_stacked<3, 3, 3, 1, 0, 1, false, 4, false, mixr1(3, 3, 3, 1)>(L, s);
-        case 19: return launch_stacked<3, 6, 3, 2>(L, s);
-        case 20: return launch_stacked<3, 6, 2, 1>(L, s);
-        case 21: return launch_stacked<3, 6, 3, 1>(L, s);
-        case 22: return launch_stacked<3, 5, 3, 2>(L, s);
-        case 23: return launch_stacked<3, 5, 2, 1>(L, s);
-        case 24: return launch_stacked<3, 5, 3, 1>(L, s);
-        case 25: return L.kodd ? launch_stacked<3, 4, 3, 2, 0, 1, false, 0, true>(L, s) : L.kmix_order <= 1 ? launch_stacked<3, 4, 3, 2, 0, 2>(L, s) : launch_stacked<3, 4, 3, 2>(L, s);
-        case 26: return launch_stacked<3, 4, 2, 1>(L, s);
-        case 27: return launch_stacked<3, 4, 3, 1>(L, s);
-        case 28: return L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 0, true>(L, s) : launch_stacked<3, 3, 3, 2>(L, s);
-        case 29: return launch_stacked<3, 3, 2, 1>(L, s);
-        case 30: return launch_stacked<3, 3, 3, 1>(L, s);
-        case 31: return L.kmix_order <= 1 ? launch_stacked<2, 6, 3, 2, 0, 2>(L, s) : launch_stacked<2, 6, 3, 2>(L, s);
-        case 32: return L.kmix_order <= 1 ? launch_stacked<2, 6, 2, 1, 0, 2>(L, s) : launch_stacked<2, 6, 2, 1>(L, s);
-        case 33: return L.kmix_order <= 1 ? launch_stacked<2, 6, 3, 1, 0, 2>(L, s) : launch_stacked<2, 6, 3, 1>(L, s);
-        case 34: return L.kmix_order <= 1 ? launch_stacked<2, 5, 3, 2, 0, 2>(L, s) : launch_stacked<2, 5, 3, 2>(L, s);
-        case 35: return L.kodd ? launch_stacked<2, 5, 2, 1, 0, 1, false, 0, true>(L, s) : L.kmix_order <= 1 ? launch_stacked<2, 5, 2, 1, 0, 2>(L, s) : launch_stacked<2, 5, 2, 1>(L, s);
-        case 36: return L.kmix_order <= 1 ? launch_stacked<2, 5, 3, 1, 0, 2>(L, s) : launch_stacked<2, 5, 3, 1>(L, s);
-        case 37: return launch_stacked<3, 6, 3, 3>(L, s);
-        case 38: return launch_stacked<3, 5, 3, 3>(L, s);
-        case 39: return launch_stacked<3, 5, 4, 1>(L, s);
-        case 40: return L.kmix_order <= 1 ? launch_stacked<3, 4, 3, 3, 0, 2>(L, s) : launch_stacked<3, 4, 3, 3>(L, s);
-        case 41: return launch_stacked<3, 4, 4, 1>(L, s);
-        case 42: return launch_stacked<3, 3, 3, 3>(L, s);
-        case 43: return launch_stacked<3, 3, 4, 1>(L, s);
-        case 44: return launch_stacked<2, 6, 3, 3>(L, s);
-        case 45: return launch_stacked<2, 6, 4, 1>(L, s);
-        case 46: return launch_stacked<2, 5, 3, 3>(L, s);
-        case 47: return launch_stacked<2, 5, 4, 1>(L, s);
-        case 48: return L.kodd ? launch_stacked<3, 2, 3, 2, 0, 1, false, 0, true>(L, s) : launch_stacked<3, 2, 3, 2>(L, s);
-        case 49: return launch_stacked<3, 2, 2, 1>(L, s);
-        case 50: return launch_stacked<3, 2, 3, 1>(L, s);
-        case 51: return launch_stacked<3, 2, 3, 3>(L, s);
-        case 52: return launch_stacked<3, 2, 4, 1>(L, s);
-        case 53: return launch_stacked<3, 6, 3, 1, 0, 1, true>(L, s);
-        case 54: return launch_stacked<3, 5, 3, 1, 0, 1, true>(L, s);
-        case 55: return launch_stacked<3, 4, 3, 1, 0, 1, true>(L, s);
-        case 56: return launch_stacked<3, 3, 3, 1, 0, 1, true>(L, s);
-        case 57: return launch_stacked<3, 2, 3, 1, 0, 1, true>(L, s);
-        case 58: return L.kmix_order <= 1 ? launch_stacked<2, 6, 3, 1, 0, 2, true>(L, s) : launch_stacked<2, 6, 3, 1, 0, 1, true>(L, s);
-        case 59: return L.kmix_order <= 1 ? launch_stacked<2, 5, 3, 1, 0, 2, true>(L, s) : launch_stacked<2, 5, 3, 1, 0, 1, true>(L, s);
-        case 60: return L.kodd ? launch_stacked<3, 2, 3, 4, 0, 1, false, 0, true>(L, s) : launch_stacked<3, 2, 3, 4>(L, s);
-        case 61: return launch_stacked<2, 4, 3, 3>(L, s);
-        case 62: return launch_stacked<2, 4, 3, 2>(L, s);
-        case 63: return launch_stacked<2, 4, 2, 1>(L, s);
-        case 64: return launch_stacked<2, 4, 3, 1>(L, s);
-        case 65: return launch_stacked<2, 3, 3, 4>(L, s);
-        case 66: return launch_stacked<2, 3, 3, 3>(L, s);
-        case 67: return launch_stacked<2, 3, 3, 2>(L, s);
-        case 68: return launch_stacked<2, 3, 2, 1>(L, s);
-        case 69: return launch_stacked<3, 2, 3, 6>(L, s);
-        case 70: return launch_stacked<3, 2, 3, 8>(L, s);
-        case 71: return launch_stacked<3, 2, 3, 12>(L, s);
-        case 72: return launch_stacked<2, 3, 3, 6>(L, s);
-        case 73: return launch_stacked<2, 3, 3, 8>(L, s);
-        case 74: return launch_stacked<2, 4, 3, 4>(L, s);
-        case 75: return launch_stacked<2, 4, 3, 6>(L, s);
-        case 76: return launch_stacked<2, 4, 3, 1, 0, 1, true>(L, s);
-        case 77: return launch_stacked<2, 3, 3, 1, 0, 1, true>(L, s);
-        case 78: return L.kpiola ? (L.kodd ? launch_stacked<3, 2, 3, 4, 0, 1, false, 4, true, true, 1>(L, s) : launch_stacked<3, 2, 3, 4, 0, 1, false, 4, false, true, 1>(L, s)) : launch_stacked<3, 2, 3, 4, 0, 1, false, 4, false, mixr1(3, 2, 3, 4)>(L, s);
-        case 79: return L.kpiola ? launch_stacked<3, 2, 3, 3, 0, 1, false, 4, false, true, 1>(L, s) : launch_stacked<3, 2, 3, 3, 0, 1, false, 4, false, mixr1(3, 2, 3, 3)>(L, s);
-        case 80: return L.kpiola ? launch_stacked<3, 2, 3, 2, 0, 1, false, 4, false, true, 1>(L, s) : launch_stacked<3, 2, 3, 2, 0, 1, false, 4, false, mixr1(3, 2, 3, 2)>(L, s);
-        case 81: return L.kpiola ? launch_stacked<3, 2, 2, 1, 0, 1, false, 4, false, true, 1>(L, s) : launch_stacked<3, 2, 2, 1, 0, 1, false, 4, false, mixr1(3, 2, 2, 1)>(L, s);
-        case 82: return L.kpiola ? launch_stacked<2, 3, 3, 4, 0, 1, false, 3, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 4, 0, mixr_wps(2, 3), false, 3, false, mixr1(2, 3, 3, 4)>(L, s);
-        case 83: return L.kpiola ? launch_stacked<2, 3, 3, 3, 0, 1, false, 3, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 3, 0, mixr_wps(2, 3), false, 3, false, mixr1(2, 3, 3, 3)>(L, s);
-        case 84: return L.kpiola ? launch_stacked<2, 3, 3, 2, 0, 1, false, 3, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 2, 0, mixr_wps(2, 3), false, 3, false, mixr1(2, 3, 3, 2)>(L, s);
-        case 85: return L.kpiola ? launch_stacked<2, 4, 3, 3, 0, 1, false, 3, false, true, 1>(L, s) : launch_stacked<2, 4, 3, 3, 0, mixr_wps(2, 4), false, 3, false, mixr1(2, 4, 3, 3)>(L, s);
-        case 86: return L.kpiola ? launch_stacked<2, 4, 3, 2, 0, 1, false, 3, false, true, 1>(L, s) : launch_stacked<2, 4, 3, 2, 0, mixr_wps(2, 4), false, 3, false, mixr1(2, 4, 3, 2)>(L, s);
-        case 87: return L.kpiola ? launch_stacked<2, 4, 2, 1, 0, 1, false, 3, false, true, 1>(L, s) : L.kodd ? launch_stacked<2, 4, 2, 1, 0, 1, false, 3, true, true>(L, s) : launch_stacked<2, 4, 2, 1, 0, mixr_wps(2, 4), false, 3, false, mixr1(2, 4, 2, 1)>(L, s);
-        case 88: return launch_stacked<3, 7, 2, 1>(L, s);
-        case 89: return launch_stacked<3, 7, 2, 1, 0, 1, true>(L, s);
-        case 90: return launch_stacked<2, 7, 3, 1>(L, s);
-        case 91: return launch_stacked<2, 7, 2, 1>(L, s);
-        case 92: return launch_stacked<2, 7, 3, 1, 0, 1, true>(L, s);
-        case 93: return launch_stacked<2, 8, 4, 1>(L, s);
-        case 94: return launch_stacked<2, 8, 3, 1, 0, 1, true>(L, s);
-        case 95: return L.kpiola ? (L.kodd ? launch_stacked<3, 2, 3, 4, 0, 1, false, 10, true, true, 1>(L, s) : launch_stacked<3, 2, 3, 4, 0, 1, false, 10, false, true, 1>(L, s)) : L.kodd ? launch_stacked<3, 2, 3, 4, 0, 1, false, 10, true, true>(L, s) : launch_stacked<3, 2, 3, 4, 0, 1, false, 10, false, true>(L, s);
-        case 96: return L.kpiola ? launch_stacked<3, 2, 3, 3, 0, 1, false, 10, false, true, 1>(L, s) : launch_stacked<3, 2, 3, 3, 0, 1, false, 10, false, true>(L, s);
-        case 97: return L.kpiola ? launch_stacked<3, 2, 3, 2, 0, 1, false, 10, false, true, 1>(L, s) : launch_stacked<3, 2, 3, 2, 0, 1, false, 10, false, true>(L, s);
-        case 98: return L.kpiola ? launch_stacked<3, 2, 2, 1, 0, 1, false, 10, false, true, 1>(L, s) : launch_stacked<3, 2, 2, 1, 0, 1, false, 10, false, true>(L, s);
-        case 99: return L.kpiola ? (L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 10, true, true, 1>(L, s) : launch_stacked<3, 3, 3, 2, 0, 1, false, 10, false, true, 1>(L, s)) : L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 10, true, true>(L, s) : launch_stacked<3, 3, 3, 2, 0, 1, false, 10, false, true>(L, s);
-        case 100: return L.kpiola ? launch_stacked<3, 3, 2, 1, 0, 1, false, 10, false, true, 1>(L, s) : launch_stacked<3, 3, 2, 1, 0, 1, false, 10, false, true>(L, s);
-        case 101: return L.kpiola ? launch_stacked<3, 3, 3, 1, 0, 1, false, 10, false, true, 1>(L, s) : launch_stacked<3, 3, 3, 1, 0, 1, false, 10, false, true>(L, s);
-        case 102: return L.kodd ? launch_stacked<3, 4, 3, 2, 0, 1, false, 10, true, true>(L, s) : launch_stacked<3, 4, 3, 2, 0, 1, false, 10, false, true>(L, s);
-        case 103: return launch_stacked<3, 4, 2, 1, 0, 1, false, 10, false, true>(L, s);
-        case 104: return launch_stacked<3, 4, 3, 1, 0, 1, false, 10, false, true>(L, s);
-        case 105: return launch_stacked<3, 5, 2, 1, 0, 1, false, 10, false, true>(L, s);
-        case 106: return launch_stacked<3, 6, 2, 1, 0, 1, false, 10, false, true>(L, s);
-        case 107: return L.kpiola ? launch_stacked<2, 3, 3, 4, 0, 1, false, 6, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 4, 0, mixr_wps(2, 3), false, 6, false, true>(L, s);
-        case 108: return L.kpiola ? launch_stacked<2, 3, 3, 3, 0, 1, false, 6, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 3, 0, mixr_wps(2, 3), false, 6, false, true>(L, s);
-        case 109: return L.kpiola ? launch_stacked<2, 3, 3, 2, 0, 1, false, 6, false, true, 1>(L, s) : launch_stacked<2, 3, 3, 2, 0, mixr_wps(2, 3), false, 6, false, true>(L, s);
-        case 110: return L.kpiola ? launch_stacked<2, 4, 3, 3, 0, 1, false, 6, false, true, 1>(L, s) : launch_stacked<2, 4, 3, 3, 0, mixr_wps(2, 4), false, 6, false, true>(L, s);
-        case 111: return L.kpiola ? launch_stacked<2, 4, 3, 2, 0, 1, false, 6, false, true, 1>(L, s) : launch_stacked<2, 4, 3, 2, 0, mixr_wps(2, 4), false, 6, false, true>(L, s);
-        case 112: return L.kpiola ? launch_stacked<2, 4, 2, 1, 0, 1, false, 6, false, true, 1>(L, s) : L.kodd ? launch_stacked<2, 4, 2, 1, 0, 1, false, 6, true, true>(L, s) : launch_stacked<2, 4, 2, 1, 0, mixr_wps(2, 4), false, 6, false, true>(L, s);
-        case 113: return launch_stacked<2, 5, 3, 2, 0, mixr_wps(2, 5), false, 6, false, true>(L, s);
-        case 114: return L.kodd ? launch_stacked<2, 5, 2, 1, 0, 1, false, 6, true, true>(L, s) : launch_stacked<2, 5, 2, 1, 0, mixr_wps(2, 5), false, 6, false, true>(L, s);
-        case 115: return L.kodd ? launch_stacked<2, 5, 3, 1, 0, 1, false, 6, true, true>(L, s) : launch_stacked<2, 5, 3, 1, 0, mixr_wps(2, 5), false, 6, false, true>(L, s);
-        case 116: return launch_stacked<2, 6, 3, 2, 0, mixr_wps(2, 6), false, 6, false, true>(L, s);
-        case 117: return launch_stacked<2, 6, 2, 1, 0, mixr_wps(2, 6), false, 6, false, true>(L, s);
-        case 118: return launch_stacked<2, 6, 3, 1, 0, mixr_wps(2, 6), false, 6, false, true>(L, s);
-        case 119: return launch_stacked<3, 6, 3, 2, 0, 1, false, 4, false, true>(L, s);
-        case 120: return launch_stacked<3, 6, 3, 1, 0, 1, false, 4, false, true>(L, s);
-        case 121: return launch_stacked<3, 6, 3, 1, 0, 1, true, 4, false, true>(L, s);
-        case 122: return launch_stacked<3, 5, 3, 1, 0, 1, true, 4, false, true>(L, s);
-        case 123: return launch_stacked<3, 4, 3, 1, 0, 1, true, 4, false, true>(L, s);
-        case 124: return launch_stacked<3, 3, 3, 1, 0, 1, true, 4, false, true>(L, s);
-        case 125: return launch_stacked<3, 2, 3, 1, 0, 1, true, 4, false, true>(L, s);
-        case 126: return launch_stacked<2, 6, 3, 1, 0, 1, true, 3, false, true>(L, s);  // (two waves per SIMD: 116-364 B of scratch)
-        case 127: return launch_stacked<2, 5, 3, 1, 0, 1, true, 3, false, true>(L, s);  // (two waves per SIMD: 116-364 B of scratch)
-        case 128: return launch_stacked<3, 6, 2, 1, 0, 1, true, 10, false, true>(L, s);
-        case 129: return launch_stacked<3, 5, 2, 1, 0, 1, true, 10, false, true>(L, s);
-        case 130: return launch_stacked<3, 4, 2, 1, 0, 1, true, 10, false, true>(L, s);
-        case 131: return launch_stacked<3, 3, 3, 1, 0, 1, true, 10, false, true>(L, s);
-        case 132: return launch_stacked<3, 2, 3, 1, 0, 1, true, 10, false, true>(L, s);
-        case 133: return launch_stacked<2, 6, 3, 1, 0, 1, true, 6, false, true>(L, s);  // (two waves per SIMD: 116-364 B of scratch)
-        case 134: return launch_stacked<2, 5, 3, 1, 0, 1, true, 6, false, true>(L, s);  // (two waves per SIMD: 116-364 B of scratch)
-        case 135: return L.kodd ? launch_stacked<3, 2, 3, 4, 0, 1, false, 1, true, true, 1>(L, s) : launch_stacked<3, 2, 3, 4, 0, 1, false, 1, false, true, 1>(L, s);
-        case 136: return launch_stacked<3, 2, 3, 3, 0, 1, false, 1, false, true, 1>(L, s);
-        case 137: return launch_stacked<3, 2, 3, 2, 0, 1, false, 1, false, true, 1>(L, s);
-        case 138: return launch_stacked<3, 2, 2, 1, 0, 1, false, 1, false, true, 1>(L, s);
-        case 139: return L.kodd ? launch_stacked<3, 3, 3, 2, 0, 1, false, 1, true, true, 1>(L, s) : launch_stacked<3, 3, 3, 2, 0, 1, false, 1, false, true, 1>(L, s);
-        case 140: return launch_stacked<3, 3, 2, 1, 0, 1, false, 1, false, true, 1>(L, s);
-        case 141: return launch_stacked<3, 3, 3, 1, 0, 1, false, 1, false, true, 1>(L, s);
-        case 142: return launch_stacked<2, 3, 3, 4, 0, 1, false, 1, false, true, 1>(L, s);
-        case 143: return launch_stacked<2, 3, 3, 3, 0, 1, false, 1, false, true, 1>(L, s);
-        case 144: return launch_stacked<2, 3, 3, 2, 0, 1, false, 1, false, true, 1>(L, s);
-        case 145: return launch_stacked<2, 4, 3, 3, 0, 1, false, 1, false, true, 1>(L, s);
-        case 146: return launch_stacked<2, 4, 3, 2, 0, 1, false, 1, false, true, 1>(L, s);
-        case 147: return launch_stacked<2, 4, 2, 1, 0, 1, false, 1, false, true, 1>(L, s);
-        case 148: return launch_stacked<3, 6, 2, 1, 0, 1, true>(L, s);
-        case 149: return launch_stacked<3, 5, 2, 1, 0, 1, true>(L, s);
-        case 150: return launch_stacked<3, 6, 2, 1, 0, 1, true, 4, false, true>(L, s);
-        case 151: return launch_stacked<3, 5, 2, 1, 0, 1, true, 4, false, true>(L, s);
-    }
-    return fail(FX_EINVAL, "internal: unknown stacked kernel %d", L.stacked_id);
+    if (L.stacked_id < 0 || L.stacked_id >= NSTACKED) return fail(FX_EINVAL, "internal: unknown stacked kernel %d", L.stacked_id);
+    const StackedShape& k = kStackedShapes[L.stacked_id];
+    // (the request-per-workgroup kernel picks its own instance from L.kodd / L.wg_mix)
+    const LaunchFn f = k.rtc == -7 ? k.base : L.kpiola ? (L.kodd ? k.pio_odd : k.pio) : L.kodd ? k.odd : (L.kmix_order <= 1 && k.lo) ? k.lo : k.base;
+    if (!f) return fail(FX_EINVAL, "internal: stacked kernel %d has no %s%s instance", L.stacked_id, L.kpiola ? "Piola " : "", L.kodd ? "8-byte" : "16-byte");
+    return f(L, s);
 }
 
 int ensure_stacked(fx_ctx* ctx, fx_element* e, int order);  // defined after the C entry points it uses
@@ -1255,13 +1173,7 @@ struct CoopShape {
     int sd, order, mt16, m4, tpw;
     bool can_piola;   // a kernel with the Piola map fused into the output rounds is instantiated
     bool piola_only;  // registered only for launches that fuse a Piola map (slower than the generic kernel otherwise)
-};
-const CoopShape kCoopShapes[] = {
-    {3, 2, 5, 1, 4, false, false},  // DG P6 tetrahedron (84 rows) with Hessians, <= 25 points
-    {3, 1, 5, 1, 2, false, false},  // DG P6 tetrahedron, values + gradient, <= 32 points
-    {3, 1, 3, 3, 2, true, false},   // N2 tetrahedron (20 x 3 = 60 rows), values + gradient: 319 vs 431 us per 25 000 requests
-    {3, 1, 3, 0, 2, true, true},    // RT2 tetrahedron (15 x 3 = 45 rows): 349 vs 252 us on the generic kernel, but the
-                             // Piola map fuses into this kernel's output rounds (generic + second pass: 616 us)
+    LaunchFn launch;  // launch_coop<...> of exactly these arguments
 };
 
 template <int SD, int ORDER, int MT16, int M4, int TPW, bool CAN_PIOLA = false, bool PIOLA_ONLY = false>
@@ -1284,32 +1196,40 @@ int launch_coop(const Launch& L, hipStream_t s) {
     return FX_OK;
 }
 
+template <int SD, int ORDER, int MT16, int M4, int TPW, bool CAN_PIOLA = false, bool PIOLA_ONLY = false>
+constexpr CoopShape coop_row() {
+    return {SD, ORDER, MT16, M4, TPW, CAN_PIOLA, PIOLA_ONLY, &launch_coop<SD, ORDER, MT16, M4, TPW, CAN_PIOLA, PIOLA_ONLY>};
+}
+constexpr CoopShape kCoopShapes[] = {
+    coop_row<3, 2, 5, 1, 4>(),              // DG P6 tetrahedron (84 rows) with Hessians, <= 25 points
+    coop_row<3, 1, 5, 1, 2>(),              // DG P6 tetrahedron, values + gradient, <= 32 points
+    coop_row<3, 1, 3, 3, 2, true>(),        // N2 tetrahedron (20 x 3 = 60 rows), values + gradient: 319 vs 431 us per 25 000 requests
+    coop_row<3, 1, 3, 0, 2, true, true>(),  // RT2 tetrahedron (15 x 3 = 45 rows): 349 vs 252 us on the generic kernel, but the
+                                            // Piola map fuses into this kernel's output rounds (generic + second pass: 616 us)
+};
+
 int run_coop(const Launch& L, hipStream_t s) {
-    switch (L.coop_id) {
-        case 0: return launch_coop<3, 2, 5, 1, 4>(L, s);
-        case 1: return launch_coop<3, 1, 5, 1, 2>(L, s);
-        case 2: return launch_coop<3, 1, 3, 3, 2, true>(L, s);
-        case 3: return launch_coop<3, 1, 3, 0, 2, true, true>(L, s);
-    }
-    return fail(FX_EINVAL, "internal: unknown cooperative kernel %d", L.coop_id);
+    if (L.coop_id < 0 || L.coop_id >= (int)(sizeof(kCoopShapes) / sizeof(kCoopShapes[0]))) return fail(FX_EINVAL, "internal: unknown cooperative kernel %d", L.coop_id);
+    return kCoopShapes[L.coop_id].launch(L, s);
 }
 
 // ---- registry of the low-order lane-local kernel: (sd, n), orders 0 and 1 -----------------
 struct SmallShape {
     int sd, n;
+    bool values_only;  // only the order-0 instance without a Piola map is compiled (the round-4 entries)
+    MatchFn matches;   // table_matches<SD, N>
+    int (*launch)(int order, const Launch&, hipStream_t);  // launch_small<SD, N>, or launch_small_values<SD, N>
 };
-// (measured against the generic kernel: (2,5) and (3,3) are slower lane-local -- 1600+ FMAs per lane -- and stay generic)
-const SmallShape kSmallShapes[] = {{2, 1}, {2, 2}, {2, 3}, {3, 1}, {3, 2}, {2, 4}, {2, 0}, {3, 0},  // degree 0 (P0 / DG0: one member, no steps): 6-19 % on the generic kernel
-                                   // round 4, VALUES ONLY: rows x members FMAs per lane stay below the HBM time of the lane's output up to ~56
-                                   // members (members / 8 FMAs per output byte), while the MFMA tiles of the other kernels are a third
-                                   // full at these row / point counts (P5 triangles, 21 rows x 25 points: 38 %)
-                                   // Measured, sustained runs, 0.8 GB (tools/instance_ab.py --own-cell [--policy no_small_values]): P5 triangles
-                                   // 345 / 264 / 247 / 551 us -> 222 / 179 / 180 / 218 at 25 / 12 / 30 / 7 points; P3 tetrahedra at 14 points
-                                   // 208 -> 165 (at 23 / 44 points the paired kernel keeps them: 187 / 161 against 176 / 178).  Tried and NOT
-                                   // registered: P6 triangles (0.82 ... 1.12 x by point count), P4 tetrahedra (1.1-1.4 x), P5 tetrahedra
-                                   // (3.7-5.4 x: 358 spilled scalar registers around the 56 x 56 coefficient stream)
-                                   {2, 5}, {3, 3}};
 constexpr int SMALL_NW = 4;
+
+// the values-only rows: nothing but the order-0 instance without a Piola map is compiled
+template <int SD, int N>
+int launch_small_values(int order, const Launch& L, hipStream_t s) {
+    if (order != 0 || L.sargs.piola) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.small_id);
+    hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 0, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
+    HIP_TRY(hipGetLastError());
+    return FX_OK;
+}
 
 template <int SD, int N>
 int launch_small(int order, const Launch& L, hipStream_t s) {
@@ -1337,60 +1257,34 @@ int launch_small(int order, const Launch& L, hipStream_t s) {
     return FX_OK;
 }
 
-int run_small(int order, const Launch& L, hipStream_t s) {
-    switch (L.small_id) {
-        case 0: return launch_small<2, 1>(order, L, s);
-        case 1: return launch_small<2, 2>(order, L, s);
-        case 2: return launch_small<2, 3>(order, L, s);
-        case 3: return launch_small<3, 1>(order, L, s);
-        case 4: return launch_small<3, 2>(order, L, s);
-        case 5: return launch_small<2, 4>(order, L, s);
-        case 6: return launch_small<2, 0>(order, L, s);
-        case 7: return launch_small<3, 0>(order, L, s);
-        case 8: case 9:
-            if (order != 0 || L.sargs.piola) break;
-            if (L.small_id == 8) hipLaunchKernelGGL((fxk::tabulate_simplex_small<2, 5, 0, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
-            if (L.small_id == 9) hipLaunchKernelGGL((fxk::tabulate_simplex_small<3, 3, 0, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
-            HIP_TRY(hipGetLastError());
-            return FX_OK;
-    }
-    return fail(FX_EINVAL, "internal: unknown small kernel %d", L.small_id);
+template <int SD, int N, bool VALUES_ONLY = false>
+constexpr SmallShape small_row() {
+    if constexpr (VALUES_ONLY) return {SD, N, true, &table_matches<SD, N>, &launch_small_values<SD, N>};
+    else return {SD, N, false, &table_matches<SD, N>, &launch_small<SD, N>};
 }
+// (measured against the generic kernel: (2,5) and (3,3) are slower lane-local -- 1600+ FMAs per lane -- and stay generic)
+constexpr SmallShape kSmallShapes[] = {
+    small_row<2, 1>(), small_row<2, 2>(), small_row<2, 3>(), small_row<3, 1>(), small_row<3, 2>(), small_row<2, 4>(),
+    small_row<2, 0>(), small_row<3, 0>(),  // degree 0 (P0 / DG0: one member, no steps): 6-19 % on the generic kernel
+    // round 4, VALUES ONLY: rows x members FMAs per lane stay below the HBM time of the lane's output up to ~56
+    // members (members / 8 FMAs per output byte), while the MFMA tiles of the other kernels are a third
+    // full at these row / point counts (P5 triangles, 21 rows x 25 points: 38 %)
+    // Measured, sustained runs, 0.8 GB (tools/instance_ab.py --own-cell [--policy no_small_values]): P5 triangles
+    // 345 / 264 / 247 / 551 us -> 222 / 179 / 180 / 218 at 25 / 12 / 30 / 7 points; P3 tetrahedra at 14 points
+    // 208 -> 165 (at 23 / 44 points the paired kernel keeps them: 187 / 161 against 176 / 178).  Tried and NOT
+    // registered: P6 triangles (0.82 ... 1.12 x by point count), P4 tetrahedra (1.1-1.4 x), P5 tetrahedra
+    // (3.7-5.4 x: 358 spilled scalar registers around the 56 x 56 coefficient stream)
+    small_row<2, 5, true>(), small_row<3, 3, true>(),
+};
 
-bool small_table_matches(int id, const fx::Program& P) {
-    switch (id) {
-        case 0: return table_matches<2, 1>(P);
-        case 1: return table_matches<2, 2>(P);
-        case 2: return table_matches<2, 3>(P);
-        case 3: return table_matches<3, 1>(P);
-        case 4: return table_matches<3, 2>(P);
-        case 5: return table_matches<2, 4>(P);
-        case 6: return table_matches<2, 0>(P);
-        case 7: return table_matches<3, 0>(P);
-        case 8: return table_matches<2, 5>(P);
-        case 9: return table_matches<3, 3>(P);
-    }
-    return false;
+int run_small(int order, const Launch& L, hipStream_t s) {
+    if (L.small_id < 0 || L.small_id >= (int)(sizeof(kSmallShapes) / sizeof(kSmallShapes[0]))) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.small_id);
+    return kSmallShapes[L.small_id].launch(order, L, s);
 }
 
 int run_fixed(const Launch& L, hipStream_t s) {
-    switch (L.fixed_id) {
-        case 0: return launch_fixed<3, 3, 1, 20, 6>(L, s);
-        case 1: return launch_fixed<3, 3, 1, 20, 5, true>(L, s);
-        case 2: return launch_fixed<3, 3, 1, 20, 4, true>(L, s);
-        case 3: return launch_fixed<3, 3, 1, 20, 3, true>(L, s);
-        case 4: return launch_fixed<3, 3, 1, 20, 8, true, 1, false>(L, s);
-        case 5: return launch_fixed<3, 3, 1, 20, 10, true, 1, false>(L, s);
-        case 6: return launch_fixed<3, 3, 1, 20, 12, true, 1, false>(L, s);
-        case 7: return launch_fixed<3, 2, 1, 45, 6, true, 1, false, 8, true>(L, s);
-        case 8: return launch_fixed<3, 4, 1, 35, 6, true, 1, false>(L, s);
-        case 9: return launch_fixed<3, 2, 1, 60, 6, true, 1, false, 4, true>(L, s);
-        case 10: return launch_fixed<3, 3, 0, 20, 2, true>(L, s);
-        case 11: return launch_fixed<3, 3, 0, 20, 3, true, 1>(L, s);
-        case 12: return launch_fixed<3, 4, 0, 35, 2, true>(L, s);
-        case 13: return launch_fixed<3, 4, 0, 35, 3, true, 1>(L, s);
-    }
-    return fail(FX_EINVAL, "internal: unknown fixed kernel %d", L.fixed_id);
+    if (L.fixed_id < 0 || L.fixed_id >= (int)(sizeof(kFixedShapes) / sizeof(kFixedShapes[0]))) return fail(FX_EINVAL, "internal: unknown fixed kernel %d", L.fixed_id);
+    return kFixedShapes[L.fixed_id].launch(L, s);
 }
 
 template <int SD, int ORDER, int KS_T, int MT_T>
@@ -1424,6 +1318,17 @@ int launch_sd(int order, const Launch& L, hipStream_t s) {
     return fail(FX_ENOTIMPL, "derivative order %d > 2 is not implemented on the device", order);
 }
 
+// A dof tile's tables or the last tile's are an odd number of doubles (`tile` rows a tile): such a request cannot leave in
+// 16-byte pieces and needs an 8-byte twin.
+constexpr bool odd_tables(long long rows, int npts, int tile = 16) {
+    return (rows * npts) % 2 != 0 || ((rows - tile * ((rows + tile - 1) / tile - 1)) * npts) % 2 != 0;
+}
+// A whole-request instance holds the request: 16 ct / g points a request may have ...
+constexpr bool holds_request(const StackedShape& k, int npts) { return npts <= 16 * k.ct / k.g; }
+// ... and is only taken when the group's points fill more than two thirds of its column tiles (measured: at 16 of 48
+// columns the in-kernel chain-rule instance runs at 18 % where the generic kernel reaches 43 %)
+constexpr bool fills_tiles(const StackedShape& k, int npts) { return 3LL * k.g * npts > 2LL * 16 * k.ct; }
+
 // `mapping` != FX_MAP_AFFINE asks for a kernel that fuses the Piola push-forward (L.fused_mapping tells
 // whether one was found; otherwise the caller runs fx_pushforward_batch after the launch)
 int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int npts, const double* pts,
@@ -1441,19 +1346,18 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
     // 14 % of the HBM peak on the cooperative kernel against 37 %; N3 triangles 29 % lane-local against 50 %)
     const bool want_piola = (mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA) && verts && e->vdim == e->sd && e->sd >= 2;
     const int TRp = fxk::stacked_tile_rows(e->sd, 1);
-    const bool pio_even = !(((long long)rows * npts) % 2) && !(((long long)(rows - TRp * ((rows + TRp - 1) / TRp - 1)) * npts) % 2);
+    const bool pio_even = !odd_tables(rows, npts, TRp);
     // (odd table sizes: 8-byte twins of the two instances RT2 / N3 tetrahedra meet at their 11- / 23-point rules)
     const bool pio_odd_twin = e->sd == 3 && ((e->n == 2 && npts > 8 && npts <= 12) || (e->n == 3 && npts > 16 && npts <= 24));
-    // ... and is there an instance that holds THIS request: the same predicates as the selection loop below (column budget of a
-    // request, more than two thirds of the group's column tiles filled) -- without the probe the cooperative and the lane-local
-    // kernel gave up their fused variants for shapes no stacked instance then took (N2 / RT2 tetrahedra at <= 8 points: generic
-    // kernel + a separate push-forward pass)
+    // ... and is there a row of the order's kind with a Piola twin that holds THIS request, by the predicates of the selection
+    // loop below -- without the probe the cooperative and the lane-local kernel gave up their fused variants for shapes no
+    // stacked instance then took (N2 / RT2 tetrahedra at <= 8 points: generic kernel + a separate push-forward pass)
     bool pio_instance = false;
     for (const StackedShape& k : kStackedShapes)
-        pio_instance = pio_instance || (k.sd == e->sd && k.n == e->n && k.rtc == (order == 0 ? -6 : order == 1 ? -2 : -3) &&
-                                        npts <= 16 * k.ct / k.g && 3LL * k.g * npts > 2LL * 16 * k.ct);
+        pio_instance = pio_instance || (k.sd == e->sd && k.n == e->n && k.rtc == (order == 0 ? -6 : order == 1 ? -2 : -3) && k.pio &&
+                                        holds_request(k, npts) && fills_tiles(k, npts));
     const bool stacked_pio_ok = want_piola && !(ctx->policy & (FX_POLICY_NO_STACKED | FX_POLICY_NO_STACKED_MIX)) && !e->raw_expansion &&
-                                stacked_has_pio(e->sd, e->n) && npts <= 48 && (pio_even || pio_odd_twin) && (long long)ntab * rows >= 15 &&
+                                npts <= 48 && (pio_even || pio_odd_twin) && (long long)ntab * rows >= 15 &&
                                 pio_instance && order <= 2;
     fxk::TabArgs& a = L.args;
     memset(&a, 0, sizeof a);
@@ -1599,11 +1503,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
             const bool want_piola = mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA;
             const bool fuse_here = want_piola && f.can_piola && verts && e->vdim == e->sd;
             if (L.fused_mapping && !fuse_here) continue;  // the cooperative kernel fuses the map, this one cannot
-            bool ok = false;
-            if (e->sd == 3 && e->n == 2) ok = table_matches<3, 2>(e->prog);
-            if (e->sd == 3 && e->n == 3) ok = table_matches<3, 3>(e->prog);
-            if (e->sd == 3 && e->n == 4) ok = table_matches<3, 4>(e->prog);
-            if (!ok) continue;
+            if (!f.matches(e->prog)) continue;
             fxk::FixedArgs<0>& fa = L.fhead;
             memset(&fa, 0, sizeof fa);
             L.fcoef.resize(e->prog.steps.size() * 3);
@@ -1707,10 +1607,10 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
         if (!nosmall && order <= 2 && npts <= 64 && rows <= 96 && reqbytes8 <= 16 * 1024 && e->d_cmat) {
             for (size_t i = 0; i < sizeof(kSmallShapes) / sizeof(kSmallShapes[0]); ++i) {
                 if (kSmallShapes[i].sd != e->sd || kSmallShapes[i].n != e->n) continue;
-                const bool values_only_shape = i >= 8;   // (the round-4 entries)
+                const bool values_only_shape = kSmallShapes[i].values_only;
                 if (values_only_shape && (order != 0 || mapping != FX_MAP_AFFINE || e->vdim != 1 || (ctx->policy & (FX_POLICY_WG_SMALL | FX_POLICY_NO_SMALL_VALUES)))) continue;
                 if (values_only_shape && e->sd == 3 && npts > 16) continue;   // (P3 tetrahedra: up to the 14-point rule)
-                if (!small_table_matches((int)i, e->prog) || (int)e->prog.steps.size() > fxk::SMALL_MAXSTEPS) continue;
+                if (!kSmallShapes[i].matches(e->prog) || (int)e->prog.steps.size() > fxk::SMALL_MAXSTEPS) continue;
                 int P = std::max(1, 64 / npts);
                 // (17-24 rows -- vector-valued degree-2 triangles -- with Hessians: 6.9 KB a request left ONE request a wave, six of 64 lanes
                 // at the 6-point rule, and the shape went to the generic kernel at 31 % of the HBM peak; up to 28 KB a wave there)
@@ -1781,7 +1681,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
         static const long long stacked_min_rows = ab_env("FIAT_AMD_STACKED_MIN_ROWS") ? atoll(ab_env("FIAT_AMD_STACKED_MIN_ROWS")) : 15;
         const long long R = (long long)ntab * rows;
         const int RT = (int)((R + 15) / 16);
-        const bool even = ((R * npts) % 2 == 0) && (((R - 16LL * (RT - 1)) * npts) % 2 == 0);
+        const bool even = !odd_tables(R, npts);
         // (after the shape-specialised registries: the tuned paired instances and the lane-local kernel keep their shapes)
         // (per-request cells: the kernel maps the points through the request's cell and a second pass applies the
         // chain rule across the derivative tables, table_mix_kernel; a Piola map is left to fx_pushforward_batch)
@@ -1815,9 +1715,6 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                         return true;
                 return false;
             };
-            // ... and only when the group's points fill more than two thirds of its column tiles (measured: at 16 of 48
-            // columns the in-kernel chain-rule instance runs at 18 % where the generic kernel reaches 43 %)
-            auto fills_tiles = [&](const StackedShape& k) { return 3LL * k.g * npts > 2LL * 16 * k.ct; };
             // (first the instances that apply the chain rule themselves, then the rest, each in table order)
             // the request-per-workgroup kernel applies the order-1 chain rule of per-request cells itself (round 4, MIX instances):
             // rules of 49..128 points, the window of P5 triangles, or policy wg_small -- the per-wave chain-rule instances yield
@@ -1850,16 +1747,15 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                 // (two waves per row tile work on two dof tiles at a time: with few rows the second pair multiplies padding -- P3 / P4
                 // tetrahedra at 70 / 74 points 424 / 406 us against 388 / 403 us on the point chunks -- so at least 70 % of those
                 // MFMA rows must be dofs; the eight-tile instances of tetrahedra, and of triangles with odd tables, run all four waves on one dof tile)
-                const bool oddm0 = ((long long)rows * npts) % 2 || ((long long)(rows - 16 * ((rows + 15) / 16 - 1)) * npts) % 2;
-                if (!(ctm == 8 && (k.sd == 3 || oddm0))) {   // (wg.hip wg_mix_pc: those instances run four waves per dof tile)
+                const bool oddm = odd_tables(rows, npts);
+                if (!(ctm == 8 && (k.sd == 3 || oddm))) {   // (wg.hip wg_mix_pc: those instances run four waves per dof tile)
                     const int rtd = (rows + 15) / 16;
                     if (10LL * rows < 7LL * 16 * 2 * ((rtd + 1) / 2)) return false;
                 }
-                const bool oddm = ((long long)rows * npts) % 2 || ((long long)(rows - 16 * ((rows + 15) / 16 - 1)) * npts) % 2;
                 return fxwg::has_mix_instance(k.sd, k.n, ctm, oddm) && fxwg::lds_bytes(k.sd, k.n, ctm) <= ctx->lds_per_cu;
             };
             // (then the request-per-workgroup instances, then the rest)
-            constexpr size_t NSH = sizeof(kStackedShapes) / sizeof(kStackedShapes[0]);
+            constexpr size_t NSH = NSTACKED;
             for (size_t i2 = 0; i2 < 3 * NSH && L.stacked_id < 0; ++i2) {
                 const size_t i = i2 % NSH, pass = i2 / NSH;
                 const StackedShape& k = kStackedShapes[i];
@@ -1891,29 +1787,23 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                     ((k.n == 3 && npts % 8 != 0 && npts != 12) || (k.n == 4 && k.rtc == -1 && npts <= 16)))
                     continue;
                 // (values-only P5 triangles where the lane-local kernel holds several requests per wave: round 4)
-                if (order == 0 && L.small_id >= 8) continue;
+                if (order == 0 && L.small_id >= 0 && kSmallShapes[L.small_id].values_only) continue;
                 if (k.rtc == -2 || k.rtc == -3 || k.rtc == -6) {  // per-request cells, order 1 / 2: chain rule across the tables inside the kernel (dof-major tiles)
                     const bool nomix = (ctx->policy & FX_POLICY_NO_STACKED_MIX) != 0;
                     if (nomix || !verts || order != (k.rtc == -2 ? 1 : k.rtc == -3 ? 2 : 0)) continue;
                     if (k.rtc == -2 && wg_mix_takes(k)) continue;
                     // the element's Piola map too (vector-valued elements: the twin with the components of a dof in one lane,
                     // 12 rows per tile in 3-D); values only: nothing else to mix, so only with the map
-                    const bool odd_pio_instance = k.sd == 3 && k.ct == 3 && ((k.n == 2 && k.g == 4) || (k.n == 3 && k.g == 2));
-                    pio = want_piola && stacked_has_pio(k.sd, k.n) && (pio_even || (pio_odd_twin && odd_pio_instance));
+                    pio = want_piola && k.pio && (pio_even || (pio_odd_twin && k.pio_odd));
                     if (k.rtc == -6 && !pio) continue;
-                    // (16-byte pieces of whole tables; three shapes have an 8-byte twin for odd table sizes: P5 triangles at the
-                    // 25-point rule, N3 and RT2 tetrahedra at the 23- and 11-point rules)
-                    mix_odd = ((long long)rows * npts) % 2 || ((long long)(rows - 16 * ((rows + 15) / 16 - 1)) * npts) % 2;
+                    // (16-byte pieces of whole tables; the rows with an 8-byte twin take odd table sizes too: P5 triangles at the
+                    // 25-point rule, N3 and RT2 tetrahedra at the 23- and 11-point rules; off-default rules of odd size: P4
+                    // tetrahedra at 17-24 points (the 23-point rule), P4 triangles at 25-32, P5 triangles at 33-48 (the 33-point rule))
+                    mix_odd = odd_tables(rows, npts);
                     // (RT2 at order 1 stays on the generic kernel: 44.7 % of the HBM peak there, 39.2 % on the twin)
                     if (pio) mix_odd = !pio_even;
-                    if (mix_odd && !pio && !((k.sd == 2 && k.n == 5 && k.ct == 2 && k.g == 1) || (k.sd == 3 && k.n == 3 && k.ct == 3 && k.g == 2) ||
-                                             (k.rtc == -3 && k.sd == 3 && k.n == 2 && k.ct == 3 && k.g == 4) ||
-                                             // off-default rules of odd size: P4 tetrahedra at 17-24 points (the 23-point rule), P4 triangles at
-                                             // 25-32, P5 triangles at 33-48 (the 33-point rule)
-                                             (k.sd == 3 && k.n == 4 && k.ct == 3 && k.g == 2) || (k.sd == 2 && k.n == 4 && k.ct == 2 && k.g == 1) ||
-                                             (k.sd == 2 && k.n == 5 && k.ct == 3 && k.g == 1)))
-                        continue;
-                    if (npts > 16 * k.ct / k.g || tighter_instance(k) || !fills_tiles(k)) continue;
+                    if (mix_odd && !pio && !k.odd) continue;
+                    if (!holds_request(k, npts) || tighter_instance(k) || !fills_tiles(k, npts)) continue;
                 } else if (wgk) {  // a request (or a group of small requests) per workgroup
                     if ((ctx->policy & FX_POLICY_NO_WG) || npts > 16 * k.ct) continue;
                     // (fewer than 49 points: the whole-request instances of the per-wave kernel -- except where several requests per
@@ -1959,7 +1849,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                     if (want_mix) {
                         // (tetrahedra: 4 column tiles with two waves per row tile or 8 with four; triangles 4 / 6 / 8 with two)
                         wg_ctw = fxwg::mix_ct(k.sd, k.n, wg_ctw);
-                        wg_odd = ((long long)rows * npts) % 2 || ((long long)(rows - 16 * ((rows + 15) / 16 - 1)) * npts) % 2;
+                        wg_odd = odd_tables(rows, npts);
                         wg_mix1 = wg_ctw > 0 && fxwg::has_mix_instance(k.sd, k.n, wg_ctw, wg_odd) && wg_mix_takes(k);
                     }
                     if (!wg_mix1) {
@@ -2031,28 +1921,22 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                     }
                 } else {
                     // (16-byte stores of whole request chunks; a few instances have an 8-byte twin for odd request sizes)
-                    const bool odd_twin = (k.sd == 3 && k.n == 4 && k.ct == 3 && k.g == 2) || (k.sd == 3 && k.n == 2 && k.ct == 3 && (k.g == 2 || k.g == 4)) ||
-                                          (k.sd == 3 && k.n == 3 && k.ct == 3 && k.g == 2) || (k.sd == 2 && k.n == 5 && k.ct == 2 && k.g == 1);
                     // (with per-request cells the 8-byte twin works as it is: the cells only enter the production phase, and the
                     // chain rule across the tables is the separate mixing pass -- P5 triangles at the 25-point rule with cells ran on
                     // the point-chunked instance at 17.6 % against 27-37 % on their own cell)
-                    if (!even && !odd_twin) continue;
-                    if (npts > 16 * k.ct / k.g || tighter_instance(k) || !fills_tiles(k)) continue;  // 16 ct / g: points one request may have
+                    // KEPT AS FOUND (DESIGN.md 10.1a, to be fixed on its own): a register-resident row (rtc > 0) has no 8-byte twin,
+                    // but the former hand list went by (sd, n, ct, g) and so let it pass wherever its whole-request sibling has
+                    // one -- <3, 3, 3, 2, 5>, policy stacked_small, order 0, an odd number of 65..79 rows.  L.kodd stays false for
+                    // rtc > 0, so run_stacked launches the row's 16-byte base instance on those odd tables, as it always did.
+                    if (!even && !k.odd) {
+                        bool sibling_odd = false;
+                        for (const StackedShape& o : kStackedShapes)
+                            sibling_odd = sibling_odd || (k.rtc > 0 && o.rtc == 0 && o.odd && o.sd == k.sd && o.n == k.n && o.ct == k.ct && o.g == k.g);
+                        if (!sibling_odd) continue;
+                    }
+                    if (!holds_request(k, npts) || tighter_instance(k) || !fills_tiles(k, npts)) continue;
                 }
-                bool ok = false;
-                if (e->sd == 3 && e->n == 6) ok = table_matches<3, 6>(e->prog);
-                if (e->sd == 3 && e->n == 5) ok = table_matches<3, 5>(e->prog);
-                if (e->sd == 3 && e->n == 4) ok = table_matches<3, 4>(e->prog);
-                if (e->sd == 3 && e->n == 3) ok = table_matches<3, 3>(e->prog);
-                if (e->sd == 2 && e->n == 6) ok = table_matches<2, 6>(e->prog);
-                if (e->sd == 2 && e->n == 5) ok = table_matches<2, 5>(e->prog);
-                if (e->sd == 3 && e->n == 2) ok = table_matches<3, 2>(e->prog);
-                if (e->sd == 2 && e->n == 4) ok = table_matches<2, 4>(e->prog);
-                if (e->sd == 2 && e->n == 3) ok = table_matches<2, 3>(e->prog);
-                if (e->sd == 3 && e->n == 7) ok = table_matches<3, 7>(e->prog);
-                if (e->sd == 2 && e->n == 7) ok = table_matches<2, 7>(e->prog);
-                if (e->sd == 2 && e->n == 8) ok = table_matches<2, 8>(e->prog);
-                if (!ok) continue;
+                if (!k.matches(e->prog)) continue;
                 int rc = ensure_stacked(ctx, const_cast<fx_element*>(e), order);
                 if (rc != FX_OK) return rc;
                 if (e->stack_state[order] != 1) continue;
@@ -2088,7 +1972,7 @@ int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int n
                 ka.lim_out = (long long)nreq * R * npts;
                 const int TRk = fxk::stacked_tile_rows(e->sd, pio ? 1 : 0);
                 ka.lim_afrag = (dofmajor ? ((long long)((rows + TRk - 1) / TRk) * ntab + 1) : (long long)(RT + 1)) * ((e->nexp + 3) / 4) * 64;
-                const bool mixr = pio || k.rtc == -3 || k.rtc == -4 || k.rtc == -5 || (k.rtc == -2 && (mix_odd || mixr1(k.sd, k.n, k.ct, k.g) || (k.sd == 3 && k.n == 6 && k.ct == 3)));
+                const bool mixr = pio || mix_odd || k.mixr;  // of the twin run_stacked will take
                 const int slots = fxk::stacked_mix_slots(e->sd, dofmajor ? ntab : 0, mixr);
                 L.klds_bytes = (fxk::WQ_CTL_DOUBLES + STACKED_NW * (fxk::stacked_image_doubles(k.ct, (e->nexp + 3) / 4, slots) + (mixr ? fxk::STACKED_KBUF : 0))) * 8;
                 if (wgk) {
@@ -3518,8 +3402,9 @@ int launch_macro_sd(int order, const fxk::TabArgs& a, int grid, int lds_bytes, h
 // ---- lane-local kernel for low-order macro elements (macro_small.hpp): (sd, n, highest order) ----
 struct MacroSmallShape {
     int sd, n, max_order;
+    MatchFn matches;  // table_matches<SD, N>
+    int (*launch)(int order, const fxk::MacroSmallArgs&, int grid, int lds_bytes, hipStream_t);  // launch_macro_small<SD, N, max_order>
 };
-const MacroSmallShape kMacroSmallShapes[] = {{2, 1, 2}, {2, 2, 2}, {2, 3, 2}, {3, 1, 2}, {3, 2, 2}, {3, 3, 1}};
 constexpr int MACRO_SMALL_NW = 4;
 
 template <int SD, int N, int ORDER>
@@ -3542,29 +3427,12 @@ int launch_macro_small(int order, const fxk::MacroSmallArgs& a, int grid, int ld
     return fail(FX_EINVAL, "internal: order %d not instantiated for the lane-local macro kernel", order);
 }
 
-int run_macro_small(int id, int order, const fxk::MacroSmallArgs& a, int grid, int lds_bytes, hipStream_t s) {
-    switch (id) {
-        case 0: return launch_macro_small<2, 1, 2>(order, a, grid, lds_bytes, s);
-        case 1: return launch_macro_small<2, 2, 2>(order, a, grid, lds_bytes, s);
-        case 2: return launch_macro_small<2, 3, 2>(order, a, grid, lds_bytes, s);
-        case 3: return launch_macro_small<3, 1, 2>(order, a, grid, lds_bytes, s);
-        case 4: return launch_macro_small<3, 2, 2>(order, a, grid, lds_bytes, s);
-        case 5: return launch_macro_small<3, 3, 1>(order, a, grid, lds_bytes, s);
-    }
-    return fail(FX_EINVAL, "internal: unknown lane-local macro kernel %d", id);
+template <int SD, int N, int MAXORDER>
+constexpr MacroSmallShape macro_small_row() {
+    return {SD, N, MAXORDER, &table_matches<SD, N>, &launch_macro_small<SD, N, MAXORDER>};
 }
-
-bool macro_small_table_matches(int id, const fx::Program& P) {
-    switch (id) {
-        case 0: return table_matches<2, 1>(P);
-        case 1: return table_matches<2, 2>(P);
-        case 2: return table_matches<2, 3>(P);
-        case 3: return table_matches<3, 1>(P);
-        case 4: return table_matches<3, 2>(P);
-        case 5: return table_matches<3, 3>(P);
-    }
-    return false;
-}
+constexpr MacroSmallShape kMacroSmallShapes[] = {macro_small_row<2, 1, 2>(), macro_small_row<2, 2, 2>(), macro_small_row<2, 3, 2>(),
+                                                 macro_small_row<3, 1, 2>(), macro_small_row<3, 2, 2>(), macro_small_row<3, 3, 1>()};
 
 }  // namespace
 
@@ -3676,10 +3544,9 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
     {   // lane-local kernel for the registered low-order shapes
         const bool nosmall = (ctx->policy & FX_POLICY_NO_MACRO_SMALL) != 0;
         const long long cmat_doubles = ((long long)e->ncell * rows * e->nexp + 1) & ~1LL;
-        for (size_t i = 0; !nosmall && i < sizeof(kMacroSmallShapes) / sizeof(kMacroSmallShapes[0]); ++i) {
-            const MacroSmallShape& m = kMacroSmallShapes[i];
-            if (m.sd != e->sd || m.n != e->n || order > m.max_order || npts > 64) continue;
-            if (!macro_small_table_matches((int)i, e->prog)) continue;
+        for (const MacroSmallShape& m : kMacroSmallShapes) {
+            if (nosmall || m.sd != e->sd || m.n != e->n || order > m.max_order || npts > 64) continue;
+            if (!m.matches(e->prog)) continue;
             const int P = std::max(1, 64 / npts);
             // rows per image round: <= 16 KB per wave, an even number of doubles per run where possible
             const long long row_bytes = (long long)P * ntab * npts * 8;
@@ -3727,7 +3594,7 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
             const int wg_per_cu = std::max(1, std::min(8, ctx->lds_per_cu / (int)lds_bytes));
             const long long nwg = (sa.nitems + MACRO_SMALL_NW - 1) / MACRO_SMALL_NW;
             const int grid = (int)std::max<long long>(1, std::min<long long>(nwg, (long long)ctx->num_cu * wg_per_cu * 2));
-            return run_macro_small((int)i, order, sa, grid, (int)lds_bytes, (hipStream_t)stream);
+            return m.launch(order, sa, grid, (int)lds_bytes, (hipStream_t)stream);
         }
     }
     fxk::TabArgs a;
