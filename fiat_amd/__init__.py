@@ -47,6 +47,7 @@ from .discontinuous_pc import DPC  # noqa: F401
 from .hierarchical import IntegratedLegendre, Legendre  # noqa: F401
 from .hdiv_trace import HDivTrace  # noqa: F401
 from .batch import Request, tabulate_requests  # noqa: F401
+from .cellmap import cell_geometry_batch, tabulate_on_cells  # noqa: F401
 
 # the element registry of the reference (FIAT/__init__.py:72-131), in-scope subset
 supported_elements = {

@@ -198,12 +198,27 @@ _EVAL_SIGS = {
                               c_void_p]),
 }
 
+# physical quadrilaterals and hexahedra through the Q1 map: the general pass and the fused kernel of 1-D Lagrange products
+_CELLMAP_SIGS = {
+    "fx_cellmap_abi_version": (c_int, []),
+    "fx_cellmap_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
+    "fx_cellmap_geometry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    "fx_cellmap_apply": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fx_cellmap_tensor_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "fx_cellmap_tensor_grid_batch": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
+}
+
 SER_LIB_PATH, serlib, SER_EXPORTS = _load_companion("serendipity", _SER_SIGS)
 SF_LIB_PATH, sflib, SF_EXPORTS = _load_companion("sforms", _SF_SIGS)
 DPC_LIB_PATH, dpclib, DPC_EXPORTS = _load_companion("dpc", _DPC_SIGS)
 TRACE_LIB_PATH, tracelib, TRACE_EXPORTS = _load_companion("trace", _TRACE_SIGS)
 HIER_LIB_PATH, hierlib, HIER_EXPORTS = _load_companion("hier", _HIER_SIGS)
 EVAL_LIB_PATH, evallib, EVAL_EXPORTS = _load_companion("eval", _EVAL_SIGS)
+CELLMAP_LIB_PATH, cellmaplib, CELLMAP_EXPORTS = _load_companion("cellmap", _CELLMAP_SIGS)
 
 # the main library the companions are linked against (its error slot): ``lib`` itself unless FIAT_AMD_LIB overrides that
 _DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libfiat_amd.so")

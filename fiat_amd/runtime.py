@@ -920,3 +920,41 @@ def sforms_tabulate_batch(table, lo, hi, order, pts, out=None, stream=None):
         ctx.handle, table.handle, host_ptr(lo), host_ptr(hi), int(order), nreq, npts, _dev_ptr(pts), _dev_ptr(out),
         _stream_ptr(stream)))
     return out
+
+
+def cellmap_kernel(sd, nn, mapping, order, nrows, vdim, npts, grid=False):
+    """Kernel instance and route of a shape on physical quadrilaterals / hexahedra (fx_cellmap_kernel; host only): ``nn`` 0
+    names the general pass, ``"fxk::cellmap_apply_kernel<sd,order,mapping> <map> P=<p>"``, ``nn`` >= 1 the fused kernel of
+    1-D Lagrange products, ``"fxk::cellmap_tensor_kernel<sd,nn,order,grid> image|stream P=<p>"`` (``grid``: npts is q)."""
+    return _route(_lib.cellmaplib.fx_cellmap_kernel, sd, nn, mapping, order, nrows, vdim, npts, bool(grid))
+
+
+def cellmap_geometry(sd, lo, hi, pts, corners, x, J, detJ, stream=None, ctx=None):
+    """fx_cellmap_geometry: pts (nreq, npts, sd), corners (nreq, 2**sd, sd) -> x, J, detJ (device tensors, written)."""
+    ctx = ctx or Context.get()
+    _lib.companion_check(_lib.cellmaplib.fx_cellmap_geometry(
+        ctx.handle, int(sd), host_ptr(lo), host_ptr(hi), int(pts.shape[0]), int(pts.shape[1]), _dev_ptr(pts), _dev_ptr(corners),
+        _dev_ptr(x), _dev_ptr(J), _dev_ptr(detJ), _stream_ptr(stream)))
+
+
+def cellmap_apply(sd, mapping, order, lo, hi, pts, corners, tab, out=None, stream=None, ctx=None):
+    """The general pass (fx_cellmap_apply) over reference tables ``tab`` (nreq, ntab, nrows, [sd,] npts) at the points they
+    were tabulated at; ``out`` None: in place."""
+    ctx = ctx or Context.get()
+    out = tab if out is None else out
+    vdim = 1 if tab.dim() == 4 else int(tab.shape[3])
+    _lib.companion_check(_lib.cellmaplib.fx_cellmap_apply(
+        ctx.handle, int(sd), int(mapping), int(order), int(tab.shape[0]), int(tab.shape[-1]), int(tab.shape[2]), vdim,
+        host_ptr(lo), host_ptr(hi), _dev_ptr(pts), _dev_ptr(corners), _dev_ptr(tab), _dev_ptr(out), _stream_ptr(stream)))
+    return out
+
+
+def cellmap_tensor_batch(sd, nodes, lo, hi, order, pts, corners, out, stream=None, grid=False, ctx=None):
+    """The fused kernel of products of sd 1-D Lagrange factors (fx_cellmap_tensor_batch / _grid_batch): ``nodes`` host
+    (sd, nn); pts (nreq, npts, sd), or with ``grid`` (nreq, sd, q); ``out`` (nreq, ntab, nn**sd, npts), written."""
+    ctx = ctx or Context.get()
+    entry = _lib.cellmaplib.fx_cellmap_tensor_grid_batch if grid else _lib.cellmaplib.fx_cellmap_tensor_batch
+    _lib.companion_check(entry(ctx.handle, int(sd), int(nodes.shape[1]), host_ptr(nodes), host_ptr(lo), host_ptr(hi), int(order),
+                               int(pts.shape[0]), int(pts.shape[2] if grid else pts.shape[1]), _dev_ptr(pts), _dev_ptr(corners),
+                               _dev_ptr(out), _stream_ptr(stream)))
+    return out
