@@ -627,11 +627,16 @@ int fx_element_dims(const fx_element* e, int* sd, int* n, int* nexp, int* ndof, 
 // ---------------------------------------------------------------------------------
 namespace {
 
+// the kernel family that takes a launch (None: an empty batch, nothing to launch)
+enum class Family { None, Generic, Coop, Fixed, Small, Stacked };
+
+// plan_launch fills the part of the winner and nothing else: a launcher reads its own family's fields only.
 struct Launch {
+    Family winner = Family::None;  // set once, by plan_launch: shape-specialised > stacked > cooperative > lane-local > generic
+    int row = -1;                  // the winner's row in its family's registry (the generic kernel has none)
     fxk::TabArgs args;
     int grid = 0, lds_bytes = 0;
     // shape-specialised path
-    int fixed_id = -1;
     fxk::FixedArgs<0> fhead;           // everything but the coefficients
     std::vector<double> fcoef;         // [nsteps][3]
     std::vector<double> fucoef;        // [nsteps][12], uniform-cell factor derivatives
@@ -645,17 +650,14 @@ struct Launch {
     // 2: K-streamed, two requests per wave (simplex_pair.hpp)
     int fkind = 0;
     // low-order lane-local kernel (simplex_small.hpp)
-    int small_id = -1;
     fxk::SmallArgs sargs;
     int sgrid = 0, slds_bytes = 0;
     // stacked-matrix kernel (simplex_stacked.hpp)
-    int stacked_id = -1;
     fxk::StackedArgs<0> khead;
     int kgrid = 0, klds_bytes = 0, kmix_order = 0;
     int wg_ct = 0;      // request-per-workgroup kernel: column tiles of the instance (its slab holds khead.gslab requests)
     int wg_mix = 0;     // ... 1: the order-1 chain rule of per-request cells on its accumulators (dof-major fragments, no mixing pass)
     // cooperative large-shape kernel
-    int coop_id = -1;
     fxk::CoopArgs cargs;
     int cgrid = 0, clds_bytes = 0;
 };
@@ -1143,7 +1145,7 @@ static_assert(stacked_table_ok(), "every stacked row has a base launcher unless 
 
 // the request-per-workgroup kernel (rtc -7; simplex_wg.hpp, compiled in wg.hip)
 int launch_wg(const Launch& L, hipStream_t s) {
-    const StackedShape& k = kStackedShapes[L.stacked_id];
+    const StackedShape& k = kStackedShapes[L.row];
     const int ct = L.wg_ct;
     hipError_t e = fxwg::launch_simplex_wg(k.sd, k.n, ct, L.kodd, L.wg_mix, L.khead, L.fcoef.data(), (int)L.fcoef.size(), L.klds_bytes, L.kgrid, L.trash, s);
     if (e != hipSuccess) return fail(FX_EHIP, "tabulate_simplex_wg<%d,%d,%d>: %s", k.sd, k.n, ct, hipGetErrorString(e));
@@ -1156,11 +1158,11 @@ int launch_wg(const Launch& L, hipStream_t s) {
 }
 
 int run_stacked(const Launch& L, hipStream_t s) {
-    if (L.stacked_id < 0 || L.stacked_id >= NSTACKED) return fail(FX_EINVAL, "internal: unknown stacked kernel %d", L.stacked_id);
-    const StackedShape& k = kStackedShapes[L.stacked_id];
+    if (L.row < 0 || L.row >= NSTACKED) return fail(FX_EINVAL, "internal: unknown stacked kernel %d", L.row);
+    const StackedShape& k = kStackedShapes[L.row];
     // (the request-per-workgroup kernel picks its own instance from L.kodd / L.wg_mix)
     const LaunchFn f = k.rtc == -7 ? k.base : L.kpiola ? (L.kodd ? k.pio_odd : k.pio) : L.kodd ? k.odd : (L.kmix_order <= 1 && k.lo) ? k.lo : k.base;
-    if (!f) return fail(FX_EINVAL, "internal: stacked kernel %d has no %s%s instance", L.stacked_id, L.kpiola ? "Piola " : "", L.kodd ? "8-byte" : "16-byte");
+    if (!f) return fail(FX_EINVAL, "internal: stacked kernel %d has no %s%s instance", L.row, L.kpiola ? "Piola " : "", L.kodd ? "8-byte" : "16-byte");
     return f(L, s);
 }
 
@@ -1209,8 +1211,8 @@ constexpr CoopShape kCoopShapes[] = {
 };
 
 int run_coop(const Launch& L, hipStream_t s) {
-    if (L.coop_id < 0 || L.coop_id >= (int)(sizeof(kCoopShapes) / sizeof(kCoopShapes[0]))) return fail(FX_EINVAL, "internal: unknown cooperative kernel %d", L.coop_id);
-    return kCoopShapes[L.coop_id].launch(L, s);
+    if (L.row < 0 || L.row >= (int)(sizeof(kCoopShapes) / sizeof(kCoopShapes[0]))) return fail(FX_EINVAL, "internal: unknown cooperative kernel %d", L.row);
+    return kCoopShapes[L.row].launch(L, s);
 }
 
 // ---- registry of the low-order lane-local kernel: (sd, n), orders 0 and 1 -----------------
@@ -1225,7 +1227,7 @@ constexpr int SMALL_NW = 4;
 // the values-only rows: nothing but the order-0 instance without a Piola map is compiled
 template <int SD, int N>
 int launch_small_values(int order, const Launch& L, hipStream_t s) {
-    if (order != 0 || L.sargs.piola) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.small_id);
+    if (order != 0 || L.sargs.piola) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.row);
     hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 0, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
     HIP_TRY(hipGetLastError());
     return FX_OK;
@@ -1278,13 +1280,13 @@ constexpr SmallShape kSmallShapes[] = {
 };
 
 int run_small(int order, const Launch& L, hipStream_t s) {
-    if (L.small_id < 0 || L.small_id >= (int)(sizeof(kSmallShapes) / sizeof(kSmallShapes[0]))) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.small_id);
-    return kSmallShapes[L.small_id].launch(order, L, s);
+    if (L.row < 0 || L.row >= (int)(sizeof(kSmallShapes) / sizeof(kSmallShapes[0]))) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.row);
+    return kSmallShapes[L.row].launch(order, L, s);
 }
 
 int run_fixed(const Launch& L, hipStream_t s) {
-    if (L.fixed_id < 0 || L.fixed_id >= (int)(sizeof(kFixedShapes) / sizeof(kFixedShapes[0]))) return fail(FX_EINVAL, "internal: unknown fixed kernel %d", L.fixed_id);
-    return kFixedShapes[L.fixed_id].launch(L, s);
+    if (L.row < 0 || L.row >= (int)(sizeof(kFixedShapes) / sizeof(kFixedShapes[0]))) return fail(FX_EINVAL, "internal: unknown fixed kernel %d", L.row);
+    return kFixedShapes[L.row].launch(L, s);
 }
 
 template <int SD, int ORDER, int KS_T, int MT_T>
@@ -1329,699 +1331,88 @@ constexpr bool holds_request(const StackedShape& k, int npts) { return npts <= 1
 // columns the in-kernel chain-rule instance runs at 18 % where the generic kernel reaches 43 %)
 constexpr bool fills_tiles(const StackedShape& k, int npts) { return 3LL * k.g * npts > 2LL * 16 * k.ct; }
 
-// `mapping` != FX_MAP_AFFINE asks for a kernel that fuses the Piola push-forward (L.fused_mapping tells
-// whether one was found; otherwise the caller runs fx_pushforward_batch after the launch)
-int plan_launch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int npts, const double* pts,
-                const double* verts, double* out, Launch& L, int mapping = 0) {
-    if (!ctx || !e) return fail(FX_EINVAL, "null context/element");
-    if (order < 0) return fail(FX_EINVAL, "negative derivative order");
-    if (order > 2) return fail(FX_ENOTIMPL, "derivative order %d > 2 is not implemented on the device", order);
-    if (nreq < 0 || npts < 0) return fail(FX_EINVAL, "negative batch size");
-    if ((nreq > 0 && npts > 0) && (!pts || !out)) return fail(FX_EINVAL, "null device pointer");
-    const int ntab = fx::binom(e->sd + order, e->sd);
-    const int rows = e->ndof * e->vdim;
-    // the element's Piola map asked for with the tabulation, and can the stacked kernel apply it to its accumulators (PIO
-    // instances: whole requests of <= 48 points, even table sizes)?  Then the cooperative and the lane-local kernel leave
-    // their fused variants of these shapes to it (coverage map with the map: N2 tetrahedra at 11 points, gradients,
-    // 14 % of the HBM peak on the cooperative kernel against 37 %; N3 triangles 29 % lane-local against 50 %)
-    const bool want_piola = (mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA) && verts && e->vdim == e->sd && e->sd >= 2;
-    const int TRp = fxk::stacked_tile_rows(e->sd, 1);
-    const bool pio_even = !odd_tables(rows, npts, TRp);
-    // (odd table sizes: 8-byte twins of the two instances RT2 / N3 tetrahedra meet at their 11- / 23-point rules)
-    const bool pio_odd_twin = e->sd == 3 && ((e->n == 2 && npts > 8 && npts <= 12) || (e->n == 3 && npts > 16 && npts <= 24));
-    // ... and is there a row of the order's kind with a Piola twin that holds THIS request, by the predicates of the selection
-    // loop below -- without the probe the cooperative and the lane-local kernel gave up their fused variants for shapes no
-    // stacked instance then took (N2 / RT2 tetrahedra at <= 8 points: generic kernel + a separate push-forward pass)
-    bool pio_instance = false;
-    for (const StackedShape& k : kStackedShapes)
-        pio_instance = pio_instance || (k.sd == e->sd && k.n == e->n && k.rtc == (order == 0 ? -6 : order == 1 ? -2 : -3) && k.pio &&
-                                        holds_request(k, npts) && fills_tiles(k, npts));
-    const bool stacked_pio_ok = want_piola && !(ctx->policy & (FX_POLICY_NO_STACKED | FX_POLICY_NO_STACKED_MIX)) && !e->raw_expansion &&
-                                npts <= 48 && (pio_even || pio_odd_twin) && (long long)ntab * rows >= 15 &&
-                                pio_instance && order <= 2;
-    fxk::TabArgs& a = L.args;
-    memset(&a, 0, sizeof a);
-    a.pts = pts;
-    a.verts = verts;
-    a.out = out;
-    a.afrag = e->d_afrag;
-    a.steps = e->d_steps;
-    a.phi0 = e->prog.phi0;
-    memcpy(a.A0, e->A0, sizeof a.A0);
-    memcpy(a.b0, e->b0, sizeof a.b0);
-    a.nreq = nreq;
-    a.npts = npts;
-    a.rows = rows;
-    a.nexp = e->nexp;
-    a.nsteps = (int)e->prog.steps.size();
-    a.KS = e->KS;
-    a.MT = e->MT;
-    a.ntab = ntab;
-    if (const char* dbg = ab_env("FIAT_AMD_DEBUG")) a.debug = atoi(dbg);  // ablation switches (measurement only)
-    if (nreq == 0 || npts == 0) {  // empty batch / empty point set: nothing to launch
-        a.nitems = 0;
-        L.grid = 0;
-        return FX_OK;
-    }
+}  // namespace
 
-    // ---- choose the work-item shape under a per-wave LDS budget ----
-    const long long budget = 32 * 1024;  // bytes per wave: >= 5 resident waves per CU
-    // (hard limit: one wave's tile may take what a CU has -- the kernel runs one wave per workgroup; reached by expansion
-    // degrees beyond 12 on tetrahedra, one column tile of 16 x nexp doubles: degree 16, 969 members, 124 KB)
-    const long long hard = std::max<long long>(64 * 1024, (long long)ctx->lds_per_cu - 4096);
-    auto phi_bytes = [&](long long cols) { return ((cols + 15) / 16) * (long long)e->KS * 64 * 8; };
-    const long long reqbytes = (long long)ntab * rows * npts * 8;
-    int P = 1, pc = npts, nchunk = 1;
-    long long stage = 0;
-    if (npts <= 64 && phi_bytes((long long)ntab * npts) + reqbytes <= budget) {
-        // whole requests, output staged through LDS; pack as many as fit in a wave
-        int pmax = 64 / npts;
-        P = 1;
-        for (int p = 2; p <= pmax; ++p)
-            if (phi_bytes((long long)p * ntab * npts) + p * reqbytes <= budget) P = p;
-        stage = P * reqbytes;
-    } else {
-        // point-chunked, direct stores
-        pc = std::min(npts, 64);
-        while (pc > 1 && phi_bytes((long long)ntab * pc) > budget) --pc;
-        if (phi_bytes((long long)ntab * pc) > hard)
-            return fail(FX_ENOTIMPL, "expansion degree too large for the LDS tile (nexp=%d, ntab=%d)", e->nexp, ntab);
-        nchunk = (npts + pc - 1) / pc;
+#include "plan_launch.hpp"  // the planner: plan_launch, run_tabulate
+
+namespace {
+
+// ---- digest of a plan (fx_plan_kernel, flag bit 4): everything of `L` that the winner's launcher reads ------------
+// Integer facts by name, the floating-point payload as one 64-bit FNV-1a hash, device tables by WHICH one was chosen --
+// no pointer value, those differ from run to run.  tools/route_sweep.py --digest pins the planner with it: a change
+// that keeps every kernel name can still move a grid, an LDS size or a coefficient.
+struct Fnv {
+    unsigned long long h = 14695981039346656037ULL;
+    void add(const double* p, size_t n) {
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < n * sizeof(double); ++i) h = (h ^ b[i]) * 1099511628211ULL;
     }
-    a.P = P;
-    a.pc = pc;
-    a.nchunk = nchunk;
-    a.nitems = nchunk > 1 ? nreq * nchunk : (nreq + P - 1) / P;
-    a.phi_doubles = (int)(phi_bytes((long long)P * ntab * pc) / 8);
-    a.stage_doubles = (int)((stage / 8 + 1) & ~1LL);
-    if (stage == 0) a.stage_doubles = 0;
-    L.lds_bytes = (a.phi_doubles + a.stage_doubles) * 8;
-    // ---- cooperative kernel for large shapes? ----
-    L.coop_id = -1;
-    {
-        const bool nocoop = (ctx->policy & FX_POLICY_NO_COOP) != 0;
-        const int rem = rows % 16;
-        const bool split = rem != 0 && rem <= 12;
-        const int mt16 = split ? rows / 16 : (rows + 15) / 16, m4 = split ? (rem + 3) / 4 : 0;
-        const int nt_need = (ntab * npts + 15) / 16;
-        if (!nocoop && npts <= 64 && e->d_coop_eint) {
-            for (size_t i = 0; i < sizeof(kCoopShapes) / sizeof(kCoopShapes[0]); ++i) {
-                const CoopShape& c = kCoopShapes[i];
-                if (c.sd != e->sd || c.order != order || c.mt16 != mt16 || c.m4 != m4 || nt_need > 4 * c.tpw) continue;
-                const bool piola = c.can_piola && (mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA) && verts && e->vdim == e->sd;
-                if (c.piola_only && !piola) continue;
-                if (piola && stacked_pio_ok) continue;
-                const int table = rows * npts;
-                // tables per output round: as many as LDS holds next to the A fragments and the chain
-                // state while two workgroups still fit a CU (fewer rounds = fewer workgroup barriers per
-                // request); when one workgroup fills the CU anyway, whatever is left of its LDS
-                const long long other = ((long long)(mt16 + m4) * e->coop_KS * 64 + 4LL * 4 * ntab * 32) * 8;
-                long long img_budget = ctx->lds_per_cu / 2 - other - 1024;
-                if (img_budget < 16 * 1024) img_budget = std::min<long long>(ctx->lds_per_cu - other - 1024, 56 * 1024);
-                int TR = std::max(1, (int)(img_budget / ((long long)table * 8)));
-                TR = std::min(TR, ntab);
-                if (piola) {  // the fused flush writes pairs: every round a whole number of them, <= 4 per thread
-                    if ((table & 1) && (TR & 1)) TR = TR > 1 ? TR - 1 : 0;
-                    while (TR > 0 && (long long)TR * table > 2 * 512 * fxk::PIOLA_SLOTS) TR -= (table & 1) ? 2 : 1;
-                    if (TR <= 0 || (((long long)ntab * table) & 1)) continue;
-                    if ((table & 1) && (ntab % TR) % 2) continue;  // the last round must be even too
-                }
-                long long img = std::max<long long>(2LL * (nt_need * 64 + 128), (long long)TR * table);
-                img = (img + 1) & ~1LL;
-                if (npts > 32) continue;  // LDS-resident chain state holds 32 points
-                long long ldsb = ((long long)(mt16 + m4) * e->coop_KS * 64 + img + 4LL * 4 * ntab * 32) * 8;
-                if (ldsb > ctx->lds_per_cu) continue;
-                fxk::CoopArgs& ca = L.cargs;
-                memset(&ca, 0, sizeof ca);
-                ca.pts = pts;
-                ca.verts = verts;
-                ca.out = out;
-                ca.afrag = e->d_afrag_coop;
-                ca.eint = e->d_coop_eint;
-                ca.edbl = e->d_coop_edbl;
-                ca.kstart = e->d_coop_kstart;
-                ca.phi0 = e->prog.phi0;
-                memcpy(ca.A0, e->A0, sizeof ca.A0);
-                memcpy(ca.b0, e->b0, sizeof ca.b0);
-                ca.nreq = nreq;
-                ca.npts = npts;
-                ca.rows = rows;
-                ca.KS = e->coop_KS;
-                ca.NT = nt_need;
-                ca.emax = e->coop_emax;
-                ca.TR = TR;
-                ca.slab_doubles = nt_need * 64 + 128;
-                ca.img_doubles = (int)img;
-                ca.debug = a.debug;
-                ca.piola = piola ? mapping : 0;
-                if (piola && !invert_small(e->sd, e->A0, ca.A0inv)) return fail(FX_EINVAL, "degenerate cell");
-                L.fused_mapping = piola;
-                L.clds_bytes = (int)ldsb;
-                int per_cu = std::max(1, std::min(2, ctx->lds_per_cu / L.clds_bytes));
-                L.cgrid = (int)std::max<long long>(1, std::min<long long>(nreq, (long long)ctx->num_cu * per_cu));
-                L.coop_id = (int)i;
-                break;
-            }
+};
+
+std::string plan_digest(const Launch& L, const fx_element* e, int order) {
+    char buf[512];
+    Fnv f;
+    buf[0] = 0;
+    switch (L.winner) {
+        case Family::None: return "fam=empty";
+        case Family::Generic: {
+            const fxk::TabArgs& a = L.args;
+            f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3);
+            snprintf(buf, sizeof buf,
+                     "fam=generic grid=%d lds=%d verts=%d afrag=%s nreq=%lld nitems=%lld npts=%d rows=%d nexp=%d nsteps=%d KS=%d MT=%d "
+                     "ntab=%d P=%d pc=%d nchunk=%d phi_doubles=%d stage_doubles=%d debug=%d",
+                     L.grid, L.lds_bytes, a.verts != nullptr, a.afrag == e->d_afrag ? "plain" : "?", a.nreq, a.nitems, a.npts,
+                     a.rows, a.nexp, a.nsteps, a.KS, a.MT, a.ntab, a.P, a.pc, a.nchunk, a.phi_doubles, a.stage_doubles, a.debug);
+            break;
         }
-    }
-    // ---- shape-specialised kernel available? ----
-    L.fixed_id = -1;
-    const bool nofixed = (ctx->policy & FX_POLICY_NO_FIXED) != 0;
-    const bool stacked_small = (ctx->policy & FX_POLICY_STACKED_SMALL) != 0;  // A/B: the stacked kernel's small-shape instances instead
-    const bool ab_small = stacked_small && !verts && mapping == FX_MAP_AFFINE;
-    if (!nofixed && !ab_small && npts <= 64) {
-        const int nt_need = (ntab * npts + 15) / 16;
-        for (size_t i = 0; i < sizeof(kFixedShapes) / sizeof(kFixedShapes[0]); ++i) {
-            const FixedShape& f = kFixedShapes[i];
-            // (half-image shapes keep the tables of each half in their own tiles: one spare tile is fine)
-            const bool nt_ok = f.nt == nt_need || (!f.fullimg && f.nt == nt_need + 1);
-            if (f.sd != e->sd || f.n != e->n || f.order != order || f.rows != rows || !nt_ok) continue;
-            {   // the image of a flush round leaves as 16-byte pieces: an even number of doubles per round (and so per request)
-                const int th = f.fullimg ? ntab : (ntab + 1) / 2;
-                if (((long long)th * rows * npts) % 2 || ((long long)(ntab - th) * rows * npts) % 2) continue;
-            }
-            const bool want_piola = mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA;
-            const bool fuse_here = want_piola && f.can_piola && verts && e->vdim == e->sd;
-            if (L.fused_mapping && !fuse_here) continue;  // the cooperative kernel fuses the map, this one cannot
-            if (!f.matches(e->prog)) continue;
-            fxk::FixedArgs<0>& fa = L.fhead;
-            memset(&fa, 0, sizeof fa);
-            L.fcoef.resize(e->prog.steps.size() * 3);
-            L.fucoef.assign(e->prog.steps.size() * 12, 0.0);
-            for (size_t k = 0; k < e->prog.steps.size(); ++k) {
-                const fx::Step& st = e->prog.steps[k];
-                L.fcoef[3 * k + 0] = st.A;
-                L.fcoef[3 * k + 1] = st.B;
-                L.fcoef[3 * k + 2] = st.C;
-                // point-independent derivatives of the collapsed-coordinate factors on the
-                // element's own cell (rows of A0 padded with zeros, expansions.py:43-63)
-                const int sd = e->sd;
-                double dfa[3] = {0, 0, 0}, dfb[3] = {0, 0, 0};
-                for (int d = 0; d < sd; ++d) {
-                    double dx = e->A0[st.codim * sd + d];
-                    double dy = st.codim + 1 < sd ? e->A0[(st.codim + 1) * sd + d] : 0.0;
-                    double dz = st.codim + 2 < sd ? e->A0[(st.codim + 2) * sd + d] : 0.0;
-                    dfb[d] = 0.5 * (dy + dz);
-                    dfa[d] = dx + dfb[d];
-                }
-                double* u = &L.fucoef[12 * k];
-                for (int d = 0; d < sd; ++d) {
-                    u[d] = st.A * dfa[d] - st.B * dfb[d];
-                    u[3 + d] = -2.0 * st.C * dfb[d];
-                }
-                int h = 0;
-                for (int d1 = 0; d1 < sd; ++d1)
-                    for (int d2 = d1; d2 < sd; ++d2) u[6 + h++] = -2.0 * st.C * dfb[d1] * dfb[d2];
-            }
-            fa.pts = pts;
-            fa.verts = verts;
-            fa.out = out;
-            const char* kk = (ctx->policy & FX_POLICY_KERNEL_IMAGE) ? "image" : (ctx->policy & FX_POLICY_KERNEL_STREAM) ? "stream" : nullptr;
-            // default: K-streamed kernel, two requests per wave when the points of two requests fit
-            // one wave (A/B: FX_POLICY_KERNEL_IMAGE | _STREAM)
-            // (pair kernel: the tables of each output half must fit half of the column tiles)
-            const bool pair_ok = npts <= 32 * (3 - f.rpw) && (f.fullimg || ntab == 1 ||
-                                                              (f.nt % 2 == 0 && (f.nt / 2) * 16 >= ((ntab + 1) / 2) * npts));
-            L.fkind = pair_ok ? 2 : 1;
-            if (kk && !strcmp(kk, "image") && !f.pair_only) L.fkind = 0;
-            if (kk && !strcmp(kk, "stream") && !f.pair_only) L.fkind = 1;
-            if (f.pair_only && L.fkind != 2) continue;
-            if (kk && !strcmp(kk, "pair") && pair_ok) L.fkind = 2;
-            L.ncu = ctx->num_cu;
-            L.trash = ctx->d_trash;
-            L.ctx = ctx;   // (the paired kernel draws its work counter at the launch, when the stream is known: work_counter)
-            fa.afrag = L.fkind >= 1 ? e->d_afrag_stream : e->d_afrag_split;
-            fa.phi0 = e->prog.phi0;
-            memcpy(fa.A0, e->A0, sizeof fa.A0);
-            memcpy(fa.b0, e->b0, sizeof fa.b0);
-            fa.nreq = nreq;
-            fa.npts = npts;
-            fa.debug = (a.debug & 0xffff) | (fuse_here ? (mapping << 16) : 0);
-            long long need = std::max<long long>((long long)f.nt * e->KS * 64, (long long)ntab * rows * npts);
-            need = (need + 1) & ~1LL;
-            if (L.fkind >= 1) {
-                {
-                    // per wave: half image (>= the K-step slab that aliases it) + 64-double dump row
-                    const int th = (L.fkind == 2 && f.fullimg) ? ntab : (ntab + 1) / 2;
-                    long long per_wave =
-                        std::max<long long>((long long)th * rows * npts, (long long)f.nt * 64 * (L.fkind == 2 ? f.rpw : 1)) + 64;
-                    per_wave = (per_wave + 1) & ~1LL;
-                    fa.lds_doubles = (int)per_wave;
-                    int rem = rows % 16;
-                    bool split = rem != 0 && rem <= 12;
-                    int nfrag = ((split ? rows / 16 : (rows + 15) / 16) + (split ? (rem + 3) / 4 : 0)) * e->KS;
-                    L.flds_bytes = (int)((nfrag * 64 + per_wave * FIXED_NW) * 8);
-                }
-                // registers bound the occupancy: ask for every workgroup the CU can hold
-                long long want = (long long)ctx->num_cu * 4;
-                const long long units = L.fkind == 2 ? (nreq + f.rpw - 1) / f.rpw : nreq;  // requests or pairs, one per wave
-                long long nwg = (units + FIXED_NW - 1) / FIXED_NW;
-                L.fgrid = (int)std::max<long long>(1, std::min<long long>(nwg, L.fkind >= 2 ? nwg : want));
-                if (L.flds_bytes > ctx->lds_per_cu) continue;
-                if (fuse_here && L.fkind != 2) continue;
-                if (fuse_here) L.fused_mapping = true;
-                L.fixed_id = (int)i;
-                break;
-            }
-            if (fuse_here) continue;
-            // 8 waves per CU (2 workgroups of 4 waves): pad the request to 1/2 of the CU's LDS
-            long long per_wave = std::max<long long>(need * 8, (long long)(ctx->lds_per_cu / 8));
-            per_wave &= ~15LL;
-            if (per_wave < need * 8) per_wave = need * 8;
-            fa.lds_doubles = (int)(per_wave / 8);
-            L.flds_bytes = (int)(per_wave * FIXED_NW);
-            if (L.flds_bytes > ctx->lds_per_cu) continue;
-            int wg_per_cu = std::max(1, ctx->lds_per_cu / L.flds_bytes);
-            long long want = (long long)ctx->num_cu * wg_per_cu;
-            long long nwg = (nreq + FIXED_NW - 1) / FIXED_NW;
-            L.fgrid = (int)std::max<long long>(1, std::min<long long>(nwg, want));
-            L.fixed_id = (int)i;
+        case Family::Coop: {
+            const fxk::CoopArgs& a = L.cargs;
+            f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3), f.add(a.A0inv, 9);
+            snprintf(buf, sizeof buf,
+                     "fam=coop row=%d grid=%d lds=%d verts=%d afrag=%s nreq=%lld npts=%d rows=%d KS=%d NT=%d emax=%d TR=%d "
+                     "slab_doubles=%d img_doubles=%d debug=%d piola=%d",
+                     L.row, L.cgrid, L.clds_bytes, a.verts != nullptr, a.afrag == e->d_afrag_coop ? "coop" : "?", a.nreq,
+                     a.npts, a.rows, a.KS, a.NT, a.emax, a.TR, a.slab_doubles, a.img_doubles, a.debug, a.piola);
+            break;
+        }
+        case Family::Fixed: {
+            const fxk::FixedArgs<0>& a = L.fhead;
+            f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3), f.add(L.fcoef.data(), L.fcoef.size()), f.add(L.fucoef.data(), L.fucoef.size());
+            snprintf(buf, sizeof buf,
+                     "fam=fixed row=%d fkind=%d grid=%d lds=%d ncu=%d verts=%d afrag=%s nreq=%lld npts=%d lds_doubles=%d debug=%d "
+                     "ncoef=%d nucoef=%d",
+                     L.row, L.fkind, L.fgrid, L.flds_bytes, L.ncu, a.verts != nullptr,
+                     a.afrag == e->d_afrag_stream ? "stream" : a.afrag == e->d_afrag_split ? "split" : "?", a.nreq, a.npts,
+                     a.lds_doubles, a.debug, (int)L.fcoef.size(), (int)L.fucoef.size());
+            break;
+        }
+        case Family::Small: {
+            const fxk::SmallArgs& a = L.sargs;
+            f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3), f.add(a.G, 9), f.add(a.coef, 3 * fxk::SMALL_MAXSTEPS);
+            snprintf(buf, sizeof buf,
+                     "fam=small row=%d grid=%d lds=%d verts=%d afrag=%s nreq=%lld nitems=%lld npts=%d rows=%d P=%d stage_doubles=%d "
+                     "debug=%d piola=%d shared_pts=%d",
+                     L.row, L.sgrid, L.slds_bytes, a.verts != nullptr, a.cmat == e->d_cmat ? "cmat" : "?", a.nreq, a.nitems,
+                     a.npts, a.rows, a.P, a.stage_doubles, a.debug, a.piola, a.shared_pts);
+            break;
+        }
+        case Family::Stacked: {
+            const fxk::StackedArgs<0>& a = L.khead;
+            f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3), f.add(a.A0inv, 9), f.add(a.G, 9), f.add(L.fcoef.data(), L.fcoef.size());
+            const char* tab = a.afrag == e->d_astack_dmp[order] ? "dmp" : a.afrag == e->d_astack_dm[order] ? "dm"
+                              : a.afrag == e->d_astack[order]   ? "plain" : "?";
+            snprintf(buf, sizeof buf,
+                     "fam=stacked row=%d grid=%d lds=%d ncu=%d verts=%d afrag=%s nreq=%lld npts=%d R=%d RT=%d gslab=%d piola=%d debug=%d "
+                     "lim_pts=%lld lim_verts=%lld lim_out=%lld lim_afrag=%lld kmix_order=%d kodd=%d kpiola=%d wg_ct=%d wg_mix=%d ncoef=%d",
+                     L.row, L.kgrid, L.klds_bytes, L.ncu, a.verts != nullptr, tab, a.nreq, a.npts, a.R, a.RT, a.gslab, a.piola,
+                     a.debug, a.lim_pts, a.lim_verts, a.lim_out, a.lim_afrag, L.kmix_order, (int)L.kodd, L.kpiola, L.wg_ct, L.wg_mix,
+                     (int)L.fcoef.size());
             break;
         }
     }
-    // ---- low-order lane-local kernel? ----
-    L.small_id = -1;
-    {
-        const bool nosmall = (ctx->policy & FX_POLICY_NO_SMALL) != 0;
-        const long long reqbytes8 = (long long)ntab * rows * npts * 8;
-        if (!nosmall && order <= 2 && npts <= 64 && rows <= 96 && reqbytes8 <= 16 * 1024 && e->d_cmat) {
-            for (size_t i = 0; i < sizeof(kSmallShapes) / sizeof(kSmallShapes[0]); ++i) {
-                if (kSmallShapes[i].sd != e->sd || kSmallShapes[i].n != e->n) continue;
-                const bool values_only_shape = kSmallShapes[i].values_only;
-                if (values_only_shape && (order != 0 || mapping != FX_MAP_AFFINE || e->vdim != 1 || (ctx->policy & (FX_POLICY_WG_SMALL | FX_POLICY_NO_SMALL_VALUES)))) continue;
-                if (values_only_shape && e->sd == 3 && npts > 16) continue;   // (P3 tetrahedra: up to the 14-point rule)
-                if (!kSmallShapes[i].matches(e->prog) || (int)e->prog.steps.size() > fxk::SMALL_MAXSTEPS) continue;
-                int P = std::max(1, 64 / npts);
-                // (17-24 rows -- vector-valued degree-2 triangles -- with Hessians: 6.9 KB a request left ONE request a wave, six of 64 lanes
-                // at the 6-point rule, and the shape went to the generic kernel at 31 % of the HBM peak; up to 28 KB a wave there)
-                const long long image_cap = ((rows > 16 && e->sd == 2) || rows > 24) ? 28 * 1024 : 12 * 1024;   // (N1 tetrahedra, 18 rows, with Hessians: 199 us at two requests a wave, 213 at four)
-                while (P > 1 && P * reqbytes8 > image_cap) --P;  // per-wave image: several workgroups per CU
-                // many rows (vector-valued elements): the MFMA contraction of the generic / stacked kernels wins over
-                // rows x members FMAs per lane (tools/coverage_map.py: 30+ rows 15-30 % here against 26-48 % there; 17-24 rows
-                // only while several requests share a wave)
-                // ... unless the Piola map of a vector-valued element on per-request cells fuses here (one pass instead of
-                // tabulation + read-modify-write of every table: tools/coverage_map.py --verts --pushforward)
-                const bool fuse_small = (mapping == FX_MAP_COVARIANT_PIOLA || mapping == FX_MAP_CONTRAVARIANT_PIOLA) && verts &&
-                                        e->vdim == e->sd && rows % e->sd == 0 && L.fixed_id < 0 && L.coop_id < 0 && !L.fused_mapping &&
-                                        !(e->sd == 3 && e->n == 2 && order == 2);  // (that instance spills 39 registers)
-                if (fuse_small && rows > 24 && order >= 1 && stacked_pio_ok) break;
-                // (36 rows of degree-1 tetrahedra -- BDM1, N2 of degree 1 -- stayed generic at 42-46 %: four members, 144 FMAs a table.
-                // Second half of round 4, tools/instance_ab.py, 0.8 GB, generic -> lane-local: BDM2 / N2 triangles with Hessians at 6 / 12
-                // points 306 / 251 -> 188 / 188 us (with cells 319 / 260 -> 188 / 188), BDM1 tetrahedra values / gradients at 4 points
-                // 159 / 216 -> 141 / 169, at 11 points 231 -> 177; with Hessians the ten tables of 36 rows are slower here, 209 -> 350: not taken)
-                const int row_cap = (e->sd == 3 && e->n == 1 && order <= 1) ? 36 : 24;
-                if (fuse_small ? rows > 36 : !values_only_shape && (rows > row_cap || (rows > 16 && P == 1))) break;
-                fxk::SmallArgs& sa = L.sargs;
-                memset(&sa, 0, sizeof sa);
-                if (fuse_small) {
-                    sa.piola = mapping;
-                    for (int q = 0; q < 9; ++q) sa.G[q] = 0.5 * e->A0[q];
-                    L.fused_mapping = true;
-                }
-                sa.pts = pts;
-                sa.verts = verts;
-                sa.out = out;
-                sa.cmat = e->d_cmat;
-                for (size_t k = 0; k < e->prog.steps.size(); ++k) {
-                    sa.coef[3 * k + 0] = e->prog.steps[k].A;
-                    sa.coef[3 * k + 1] = e->prog.steps[k].B;
-                    sa.coef[3 * k + 2] = e->prog.steps[k].C;
-                }
-                sa.phi0 = e->prog.phi0;
-                memcpy(sa.A0, e->A0, sizeof sa.A0);
-                memcpy(sa.b0, e->b0, sizeof sa.b0);
-                sa.nreq = nreq;
-                sa.nitems = (nreq + P - 1) / P;
-                sa.npts = npts;
-                sa.rows = rows;
-                sa.P = P;
-                sa.stage_doubles = (int)(((long long)P * ntab * rows * npts + 1) & ~1LL);
-                sa.debug = a.debug;
-                L.slds_bytes = sa.stage_doubles * 8 * SMALL_NW;
-                const int wg_per_cu = std::max(1, std::min(8, ctx->lds_per_cu / std::max(1, L.slds_bytes)));
-                const long long nwg = (sa.nitems + SMALL_NW - 1) / SMALL_NW;
-                L.sgrid = (int)std::max<long long>(1, std::min<long long>(nwg, (long long)ctx->num_cu * wg_per_cu * 4));
-                L.small_id = (int)i;
-                break;
-            }
-        }
-    }
-    // ---- stacked-matrix kernel (requests on the element's own cell, large shapes)? ----
-    L.stacked_id = -1;
-    {
-        const bool nostacked = (ctx->policy & FX_POLICY_NO_STACKED) != 0;
-        // (fewer stacked rows: the production of the B fragments is no longer amortised over enough row tiles)
-        // (measured, tools/coverage_map.py: values-only requests of P3 / P4 tetrahedra, 20 / 35 rows, run at 45 / 30 % of the HBM
-        // peak here against 23 / 13 % on the generic kernel; below one row tile nothing is left to amortise)
-        // (15 rows: values-only P4 triangles 27-30 % lane-local -> 38-49 % here; 10 rows -- P3 triangles, P2 tetrahedra -- stay
-        // lane-local, 39-43 % against 34-39 %)
-        // (round 3, tools/coverage_map.py --audit: since the lane-local kernel packs several requests per lane group it serves
-        // the 15-row tables faster wherever it holds them -- 6 / 16 / 25 / 32 points: 165 / 157 / 211 / 157 us against
-        // 249 / 191 / 412 / 282 us here -- so below one full row tile this kernel only takes what the lane-local one refuses)
-        static const long long stacked_min_rows = ab_env("FIAT_AMD_STACKED_MIN_ROWS") ? atoll(ab_env("FIAT_AMD_STACKED_MIN_ROWS")) : 15;
-        const long long R = (long long)ntab * rows;
-        const int RT = (int)((R + 15) / 16);
-        const bool even = !odd_tables(R, npts);
-        // (after the shape-specialised registries: the tuned paired instances and the lane-local kernel keep their shapes)
-        // (per-request cells: the kernel maps the points through the request's cell and a second pass applies the
-        // chain rule across the derivative tables, table_mix_kernel; a Piola map is left to fx_pushforward_batch)
-        // (the lane-local kernel keeps the shapes no stacked instance takes -- degrees 1 and 2 on triangles, degree 1 on
-        // tetrahedra, fewer than 16 stacked rows -- and per-request cells, where it applies the chain rule itself; elsewhere
-        // the MFMA contraction wins: tools/coverage_map.py, P3 / P4 triangles and P2 tetrahedra with derivatives 26-52 % -> 50-69 %)
-        // (order 2 with per-request cells: the rtc -3 instances beat the lane-local kernel on P4 triangles and P2 tetrahedra,
-        // 21 -> 58 % and 19 -> 38 % of the HBM peak, tools/coverage_map.py --verts --order 2 [--policy no_small])
-        const bool small_keeps = L.small_id >= 0 && verts;
-        // (round 3 audit, ABAB with tools/instance_ab.py [--policy no_small]: gradients of P4 triangles 264 / 213 / 260 / 293 / 218 us
-        // lane-local at 12 / 16 / 24 / 25 / 32 points against 193 / 164 / 162 / 259 / 164 us on the rtc -2 instances; Hessians of P3
-        // triangles at 15 / 16 points 280 / 259 against 216 / 202 us -- level or behind at the other sizes; P3 triangles and P2
-        // tetrahedra with gradients stay lane-local, 151-220 against 177-262 us)
-        const bool over_small = (order == 2 && ((e->sd == 2 && e->n >= 4) || (e->sd == 3 && e->n >= 2) ||
-                                                (e->sd == 2 && e->n == 3 && npts >= 13 && npts <= 16))) ||
-                                (order == 1 && e->sd == 2 && e->n == 4);
-        // (round 3, tools/coverage_map.py --audit + tools/instance_ab.py --own-cell, ABAB at 1.5 GB of tables: on the element's own
-        // cell the stacked kernel now beats the paired instances of P3 tetrahedra with gradients outside the 21..24-point
-        // benchmark shape -- 12 / 14 / 28 / 32 / 44 points: 294 / 296 / 304 / 282 / 284 us paired, 270 / 256 / 259 / 249 / 257 us
-        // here -- and of P4 tetrahedra, 400 / 373 us -> 316 / 303 us at 22 / 24 points; with per-request cells the paired kernel
-        // applies the chain rule on its accumulators and keeps every shape, 285-345 us against 365-750 us.  Those entries yield
-        // when an instance here holds the request.)
-        const bool fixed_yields = L.fixed_id >= 0 && !verts && !L.fused_mapping && order == 1 && e->sd == 3 &&
-                                  ((e->n == 3 && kFixedShapes[L.fixed_id].nt != 6) || e->n == 4);
-        if (!nostacked && (L.fixed_id < 0 || fixed_yields) && (!small_keeps || over_small) && !L.fused_mapping && !e->raw_expansion && order <= 2) {
-            // among the instances of one kind that hold the request, the one with the fewest padding columns
-            auto tighter_instance = [&](const StackedShape& k) {
-                for (const StackedShape& o : kStackedShapes)
-                    if (o.sd == k.sd && o.n == k.n && o.rtc == k.rtc && 16 * o.ct / o.g >= npts &&
-                        (16 * o.ct / o.g < 16 * k.ct / k.g || (16 * o.ct / o.g == 16 * k.ct / k.g && o.ct < k.ct)))
-                        return true;
-                return false;
-            };
-            // (first the instances that apply the chain rule themselves, then the rest, each in table order)
-            // the request-per-workgroup kernel applies the order-1 chain rule of per-request cells itself (round 4, MIX instances):
-            // rules of 49..128 points, the window of P5 triangles, or policy wg_small -- the per-wave chain-rule instances yield
-            auto wg_mix_takes = [&](const StackedShape& k) {
-                if ((ctx->policy & (FX_POLICY_NO_WG | FX_POLICY_NO_STACKED_MIX)) || !verts || order != 1 || npts > 128) return false;
-                // (49..64 points, two requests per slab: tools/instance_ab.py [--policy wg_small], sustained, 0.8 GB -- N3 / RT3 tetrahedra at
-                // 57 / 50 points 315 / 316 -> 199 / 190 us, P3 / P4 / P5 / P6 at 57 points 384 / 412 / 464 / 544 -> 279 / 328 / 333 / 434, P6
-                // triangles at 49 / 60 points 427 / 394 -> 302 / 253, P5 at 55 points 515 -> 313: the former routes were a second
-                // 48-point chunk that is mostly padding, or a four-tile whole-request instance plus the table-mixing pass)
-                // (... and two windows the off-default audits found, tools/coverage_map.py --audit --verts --qdeg-offset -1, confirmed in
-                // sustained runs: vector-valued degree-3 tetrahedra at 13..15 points -- N3 / RT3 / BDM3 at the 14-point rule 407 / 352 / 374 ->
-                // 229 / 174 / 181 us, nine requests per slab against the three-request instance + table-mixing pass -- and tables of an odd
-                // number of doubles at 17..48 points, which only the point chunks or a whole-request instance + mixing pass held: P5
-                // triangles at 19 points 589 -> 307 us, P4 tetrahedra at 31 points 401 -> 314)
-                // (where the per-wave kernel has an 8-byte twin of its chain-rule instance it keeps the odd tables: N3 tetrahedra at the
-                // 23-point rule 198 us there against 213 here)
-                const bool odd_pt = ((long long)rows * npts) % 2 != 0;
-                const bool twin2 = (k.sd == 3 && (k.n == 3 || k.n == 4) && npts <= 24) || (k.sd == 2 && k.n == 5 && npts >= 25);
-                const bool window = npts > 48 || (k.sd == 2 && k.n == 5 && npts >= 25 && npts <= 33) ||
-                                    (k.sd == 3 && k.n == 3 && e->vdim > 1 && npts >= 13 && npts <= 15) ||
-                                    // (degree >= 4 tetrahedra at 13..15 points, nine requests per slab: P4 / P5 / P6 at 14 points 403 / 485 / 580 ->
-                                    // 272 / 292 / 393 us)
-                                    (k.sd == 3 && k.n >= 4 && npts >= 13 && npts <= 15) ||
-                                    (odd_pt && npts >= 17 && npts <= 48 && !twin2);
-                if (!(window || (ctx->policy & FX_POLICY_WG_SMALL))) return false;
-                const int g = npts > 64 ? 1 : std::min(12, 128 / npts);
-                const int ctn = std::max(4, (g * npts + 15) / 16);
-                const int ctm = fxwg::mix_ct(k.sd, k.n, ctn);
-                if (ctm == 0) return false;
-                // (two waves per row tile work on two dof tiles at a time: with few rows the second pair multiplies padding -- P3 / P4
-                // tetrahedra at 70 / 74 points 424 / 406 us against 388 / 403 us on the point chunks -- so at least 70 % of those
-                // MFMA rows must be dofs; the eight-tile instances of tetrahedra, and of triangles with odd tables, run all four waves on one dof tile)
-                const bool oddm = odd_tables(rows, npts);
-                if (!(ctm == 8 && (k.sd == 3 || oddm))) {   // (wg.hip wg_mix_pc: those instances run four waves per dof tile)
-                    const int rtd = (rows + 15) / 16;
-                    if (10LL * rows < 7LL * 16 * 2 * ((rtd + 1) / 2)) return false;
-                }
-                return fxwg::has_mix_instance(k.sd, k.n, ctm, oddm) && fxwg::lds_bytes(k.sd, k.n, ctm) <= ctx->lds_per_cu;
-            };
-            // (then the request-per-workgroup instances, then the rest)
-            constexpr size_t NSH = NSTACKED;
-            for (size_t i2 = 0; i2 < 3 * NSH && L.stacked_id < 0; ++i2) {
-                const size_t i = i2 % NSH, pass = i2 / NSH;
-                const StackedShape& k = kStackedShapes[i];
-                bool mix_odd = false, pio = false;
-                int wg_g = 1, wg_ctw = 0;
-                bool wg_mix1 = false, wg_odd = false;
-                const bool inmix = k.rtc == -2 || k.rtc == -3 || k.rtc == -4 || k.rtc == -5 || k.rtc == -6;  // chain rule / Piola map inside the kernel
-                const bool chunked = k.rtc == -1 || k.rtc == -4 || k.rtc == -5;
-                const bool wgk = k.rtc == -7;
-                if (pass != (inmix ? 0u : wgk ? 1u : 2u)) continue;
-                if (small_keeps && k.rtc != -3 && k.rtc != -2) continue;
-                if (k.sd != e->sd || k.n != e->n) continue;
-                // small shapes with register-resident fragments: A/B partner of the paired kernel only (measured
-                // equal on C2, 302 vs 303 us -- both sit on the store-path plateau -- and the paired kernel's
-                // recurrence derivatives are two digits more accurate), opt-in with FIAT_AMD_STACKED_SMALL=1
-                if (k.rtc > 0 ? (RT != k.rtc || verts || !stacked_small) : (R < stacked_min_rows || (R < 16 && L.small_id >= 0))) continue;
-                // (per-request cells with derivatives on the low-degree shapes: the second pass over the tables costs more
-                // than the generic kernel's in-kernel chain rule -- tools/small_vs_stacked.py --verts, 18-29 % against 25-48 %)
-                if (!inmix && verts && order >= 1 && (k.n <= 2 || (k.sd == 2 && k.n <= 4))) continue;
-                // (the same for vector-valued degree-3 tetrahedra at up to 16 points, round 3 audit: N3 / RT3 / BDM3 with Hessians at
-                // 11 / 16 points 525 / 450, 447 / 425, 492 / 461 us on the three-request instance plus mixing pass against 404 / 312,
-                // 375 / 288, 426 / 312 us generic; N3 with gradients 392 / 324 against 338 / 221, but 379 against 398-444 at 14 points: kept there)
-                if (!inmix && verts && k.sd == 3 && k.n == 3 && e->vdim > 1 && (order == 2 ? npts <= 16 : order == 1 && (npts <= 12 || npts == 16))) continue;
-                // (own cell, gradients of P3 / P4 triangles where the lane-local kernel holds the request -- round 3, ABAB with
-                // tools/instance_ab.py --own-cell [--policy no_stacked]: P3 at 6 / 7 / 10 / 15 / 25 points 195 / 197 / 172 / 170 / 199 us
-                // here against 149 / 149 / 144 / 157 / 149 us lane-local, while 8 / 12 / 16 / 24 points are level or better here;
-                // P4 at odd sizes up to 16 points falls to the point-chunked instance, 407 us against 264 us at 15 points)
-                if (!verts && order == 1 && L.small_id >= 0 && k.sd == 2 &&
-                    ((k.n == 3 && npts % 8 != 0 && npts != 12) || (k.n == 4 && k.rtc == -1 && npts <= 16)))
-                    continue;
-                // (values-only P5 triangles where the lane-local kernel holds several requests per wave: round 4)
-                if (order == 0 && L.small_id >= 0 && kSmallShapes[L.small_id].values_only) continue;
-                if (k.rtc == -2 || k.rtc == -3 || k.rtc == -6) {  // per-request cells, order 1 / 2: chain rule across the tables inside the kernel (dof-major tiles)
-                    const bool nomix = (ctx->policy & FX_POLICY_NO_STACKED_MIX) != 0;
-                    if (nomix || !verts || order != (k.rtc == -2 ? 1 : k.rtc == -3 ? 2 : 0)) continue;
-                    if (k.rtc == -2 && wg_mix_takes(k)) continue;
-                    // the element's Piola map too (vector-valued elements: the twin with the components of a dof in one lane,
-                    // 12 rows per tile in 3-D); values only: nothing else to mix, so only with the map
-                    pio = want_piola && k.pio && (pio_even || (pio_odd_twin && k.pio_odd));
-                    if (k.rtc == -6 && !pio) continue;
-                    // (16-byte pieces of whole tables; the rows with an 8-byte twin take odd table sizes too: P5 triangles at the
-                    // 25-point rule, N3 and RT2 tetrahedra at the 23- and 11-point rules; off-default rules of odd size: P4
-                    // tetrahedra at 17-24 points (the 23-point rule), P4 triangles at 25-32, P5 triangles at 33-48 (the 33-point rule))
-                    mix_odd = odd_tables(rows, npts);
-                    // (RT2 at order 1 stays on the generic kernel: 44.7 % of the HBM peak there, 39.2 % on the twin)
-                    if (pio) mix_odd = !pio_even;
-                    if (mix_odd && !pio && !k.odd) continue;
-                    if (!holds_request(k, npts) || tighter_instance(k) || !fills_tiles(k, npts)) continue;
-                } else if (wgk) {  // a request (or a group of small requests) per workgroup
-                    if ((ctx->policy & FX_POLICY_NO_WG) || npts > 16 * k.ct) continue;
-                    // (fewer than 49 points: the whole-request instances of the per-wave kernel -- except where several requests per
-                    // workgroup are robustly ahead in sustained runs, tools/instance_ab.py --own-cell [--policy wg_small], 0.8 GB:
-                    // P5 triangles with derivatives at 25..33 points 232 / 183 / 252 -> 189 / 169 / 225 us, degree-6 tetrahedra with
-                    // Hessians at 33..48 points 432 -> 352 us.  Elsewhere the two are within +-10 % of each other with either sign,
-                    // and the map's short interleaved runs disagree with the sustained ones: opt-in, policy wg_small)
-                    // (vector-valued degree-3 tetrahedra of 180 rows a table -- BDM3, N2 of degree 3 -- at 17..24 points with cells, values:
-                    // 892 -> 744 us at the 23-point rule in 4 GB batches.  What the 0.8 GB runs of the audits showed beside it -- their
-                    // other orders, 13..15 points on the own cell, 49..64 points with derivatives -- is within +-4 % at 4 GB: not taken)
-                    // (... and on the own cell: 904 -> 742 us; gradients / Hessians there 1.07 / 1.01, RT3 / N3 values 0.91 / 1.10: not taken)
-                    const bool vec3_rows = k.sd == 3 && k.n == 3 && e->vdim > 1 && rows >= 160;
-                    // (after the kernel's second half of round 4, sustained default / wg_small sweep over 135 shapes, own cell and cells:
-                    // degree >= 5 tetrahedra at 13..15 points, nine requests per slab -- P5 / P6 at 14 points, values / gradients / Hessians
-                    // 352 / 272 / 302 -> 316 / 237 / 236 us and 465 / 371 / 439 -> 401 / 328 / 314, with cells 368 / - / 571 -> 351 / - / 472 and
-                    // 477 / - / 697 -> 422 / - / 549; P4 with Hessians 208 -> 187, with cells 477 -> 438; values of degree >= 5 at 25..32
-                    // points, four per slab, 363 / 466 -> 319 / 410.  Confirmed in 4 GB batches (CAP_GB=4): 0.91-0.97 of the per-wave
-                    // instances there, 0.89 / 0.91 at 25..32 points -- while P6 with Hessians at the 23-point rule, 438 -> 366 us at 0.8 GB,
-                    // is 1.04 at 4 GB and 7.51 against 6.93 ms in bench.py --workload dg6tet: heavy requests are few at 0.8 GB and the
-                    // two kernels quantise differently over the chip; windows are taken from the larger batches)
-                    const bool hi14 = k.sd == 3 && npts >= 13 && npts <= 15 && (k.n >= 5 || (k.n == 4 && order == 2));
-                    const bool hi_more = k.sd == 3 && k.n >= 5 && order == 0 && npts >= 25 && npts <= 32;
-                    const bool small_window = (k.sd == 2 && k.n == 5 && order >= 1 && npts >= 25 && npts <= 33) ||
-                                              (k.sd == 3 && k.n == 6 && order == 2 && npts >= 33 && npts <= 48) || hi14 || (hi_more && !verts);
-                    // per-request cells with gradients: the chain rule on the accumulators (MIX instances); other orders with
-                    // cells: values straight from the kernel, derivatives + the table-mixing pass
-                    const bool nomix = (ctx->policy & FX_POLICY_NO_STACKED_MIX) != 0;
-                    const bool want_mix = verts && order == 1 && !nomix;
-                    // (tables of an odd number of doubles at 17..48 points had only the point chunks: P5 triangles with gradients at 19
-                    // points 361 -> 201 us, values of P4 tetrahedra at 31 points 515 -> 394; with cells 586 -> 459)
-                    // (not where a whole-request instance has an 8-byte twin: values of P4 tetrahedra at the 23-point rule 315 us there,
-                    // 422 here)
-                    const bool twin1 = (k.sd == 3 && (k.n == 3 || k.n == 4) && npts <= 24) || (k.sd == 2 && k.n == 5 && npts >= 25 && npts <= 32);
-                    const bool odd_window = !even && npts >= 17 && npts <= 48 && (!verts || order == 0) && !twin1;
-                    if (npts <= 48 && !(ctx->policy & FX_POLICY_WG_SMALL) && !(small_window && (!verts || want_mix)) && !odd_window &&
-                        !(order == 0 && vec3_rows && npts >= 17 && npts <= 24) &&
-                        !(verts && order != 1 && (hi14 || hi_more)) &&
-                        !(want_mix && wg_mix_takes(k)))
-                        continue;
-                    // requests per slab of <= 128 columns and the instance's column tiles
-                    wg_g = npts > 64 ? 1 : std::min(12, 128 / npts);
-                    wg_ctw = std::max(4, (wg_g * npts + 15) / 16);
-                    if (want_mix) {
-                        // (tetrahedra: 4 column tiles with two waves per row tile or 8 with four; triangles 4 / 6 / 8 with two)
-                        wg_ctw = fxwg::mix_ct(k.sd, k.n, wg_ctw);
-                        wg_odd = odd_tables(rows, npts);
-                        wg_mix1 = wg_ctw > 0 && fxwg::has_mix_instance(k.sd, k.n, wg_ctw, wg_odd) && wg_mix_takes(k);
-                    }
-                    if (!wg_mix1) {
-                        if (verts && order >= 1 && npts <= 48 && !(ctx->policy & FX_POLICY_WG_SMALL) && !(hi14 && order == 2)) continue;
-                        // (65..96 points -- five or six column tiles -- with a short K loop: a stage is a few dozen MFMAs and the
-                        // per-request recurrence + barriers dominate.  tools/instance_ab.py --own-cell [--policy no_wg], 0.8 GB, this
-                        // kernel against the point chunks: P4 tetrahedra at 70 points, values / gradients 779 / 435 against 455 / 270 us,
-                        // P3 528 / 232 against 345 / 217, P5 triangles at 79 points 556 / 358 against 334 / 234, P6 triangles values
-                        // 455 against 320 -- while degree >= 5 tetrahedra (K steps >= 14) and P6 triangles with Hessians win, as does
-                        // everything at 97..128 points.  Policy wg_small opts in regardless.)
-                        wg_odd = !even;
-                        wg_ctw = std::max(4, (wg_g * npts + 15) / 16);
-                        if (wg_ctw == 7) wg_ctw = 8;        // (no seven-tile instance)
-                        if (wg_ctw == 5) {                   // one wave per row tile on 5 column tiles, or two on 3 + 3: the fewer MFMA slots per wave
-                            const long long one = (long long)((RT + 3) / 4) * 5, two = (long long)((RT + 1) / 2) * 3;
-                            // (the one-wave-per-row-tile layout holds ONE request per slab: twelve requests of 6 points -- policy
-                            // wg_small, 72 columns -- were planned onto it and refused by the launch, hipErrorInvalidValue)
-                            if (two < one || wg_g > 1) wg_ctw = 6;
-                        }
-                        // (... except the instances of one wave per row tile on five column tiles, since the recurrence coefficients are
-                        // fetched ahead and the last tile of a group leaves under the next group's MFMAs (second half of round 4;
-                        // sustained, same tool): values of P4 tetrahedra at 74 / 75 points 358 / 394 us against 432 / 429 on the point
-                        // chunks, RT3 values / P3 Hessians at 74 points 175 / 164 against 202 / 197, P5 triangles with gradients at 65 / 72 /
-                        // 79 points 240 / 187 / 224 against 261 / 240 / 235 -- while two waves per row tile on six column tiles still lose
-                        // with few rows: P6 triangles, values at 79 points 359 against 296, P3 tetrahedra at 70 points 460 against 348)
-                        if (npts > 64 && (wg_g * npts + 15) / 16 <= 6 && !(ctx->policy & FX_POLICY_WG_SMALL) &&
-                            !((e->nexp + 3) / 4 >= 14 || (k.sd == 2 && k.n == 6 && order == 2) || wg_ctw == 5))
-                            continue;
-                        if (!fxwg::has_instance(k.sd, k.n, wg_ctw, wg_odd)) continue;
-                    }
-                    // (49..64 points: where a whole-request instance of four column tiles exists it keeps the rule)
-                    // (... except degree >= 5 tetrahedra: two requests per slab 0.87-0.93 of the four-tile instance at 57 points)
-                    if (!wg_mix1 && npts > 48 && npts <= 64 && even && !(ctx->policy & FX_POLICY_WG_SMALL) && !(k.sd == 3 && k.n >= 5)) {
-                        bool whole = false;
-                        for (const StackedShape& o : kStackedShapes)
-                            whole = whole || (o.sd == k.sd && o.n == k.n && o.rtc == 0 && o.g == 1 && o.ct == 4);
-                        if (whole) continue;
-                    }
-                    if (nreq + 3LL * ctx->num_cu > 0x7fffffffLL) continue;
-                } else if (chunked) {  // point-chunked: whatever the whole-request instances above did not take
-                    if (npts < 13 || nreq * (long long)((npts + 16 * k.ct - 1) / (16 * k.ct)) > 0x7fffffffLL) continue;
-                    if ((k.rtc == -1 || k.rtc == -4) && k.sd == 3 && (k.n == 6 || k.n == 5)) {
-                        // two-tile or three-tile chunks: the fewer column tiles.  Measured (tools/instance_ab.py --own-cell, 0.8 GB): degree 6
-                        // at the 122-point rule, values / gradients / Hessians 581 / 469 / 540 us on 48-point chunks (9 tiles) -> 535 / 364 /
-                        // 353 us on 32-point chunks (8 tiles); at 57 points (6 -> 4 tiles) gradients 426 us.  On a tie (74 points: 6 tiles
-                        // either way) degree 6 is faster on 48-point chunks (402 against 448 us) and degree 5 within the spread of the two
-                        // measurement protocols (361-370 us in sustained runs, 410-428 in the map's short ones, against 385-400): ties stay
-                        // on 48-point chunks
-                        const long long t2 = 2LL * ((npts + 31) / 32), t3 = 3LL * ((npts + 47) / 48);
-                        if ((k.ct == 2) != (t2 < t3)) continue;
-                    }
-                    if (inmix) {  // ... with the chain rule inside: rules of more than one chunk
-                        const bool nomix = (ctx->policy & FX_POLICY_NO_STACKED_MIX) != 0;
-                        if (nomix || !verts || order != (k.rtc == -4 ? 1 : 2) || npts <= 16 * k.ct) continue;
-                        if (k.rtc == -4 && wg_mix_takes(k)) continue;
-                        // (49..64 points: the second chunk of 48 is mostly padding.  Round 3 audit, ABAB tools/instance_ab.py
-                        // [--policy no_stacked_mix]: where a whole-request instance of four column tiles exists and the stacked
-                        // matrix is small, that instance plus the mixing pass is faster -- gradients of P3 / P4 / P5 tetrahedra at
-                        // 50 points 532 / 557 / 614 -> 392 / 428 / 516 us, P5 / P6 triangles 567 / 479 -> 421 / 423 us, Hessians of P3
-                        // tetrahedra and P5 triangles 512 / 513 -> 411 / 424 us; from ~250 stacked rows on the pass over the tables
-                        // costs more than the padding: N3 tetrahedra 318 against 395 us, Hessians of P4 / P5 tetrahedra 397 / 446
-                        // against 467 / 539 us, and of P6 triangles at 168 rows 397 against 426 us)
-                        if (npts <= 64 && even && R <= 224 && !(order == 2 && k.sd == 2 && k.n == 6)) {
-                            bool whole = false;
-                            for (const StackedShape& o : kStackedShapes)
-                                whole = whole || (o.sd == k.sd && o.n == k.n && o.rtc == 0 && o.g == 1 && o.ct == 4);
-                            if (whole) continue;
-                        }
-                    }
-                } else {
-                    // (16-byte stores of whole request chunks; a few instances have an 8-byte twin for odd request sizes)
-                    // (with per-request cells the 8-byte twin works as it is: the cells only enter the production phase, and the
-                    // chain rule across the tables is the separate mixing pass -- P5 triangles at the 25-point rule with cells ran on
-                    // the point-chunked instance at 17.6 % against 27-37 % on their own cell)
-                    // KEPT AS FOUND (DESIGN.md 10.1a, to be fixed on its own): a register-resident row (rtc > 0) has no 8-byte twin,
-                    // but the former hand list went by (sd, n, ct, g) and so let it pass wherever its whole-request sibling has
-                    // one -- <3, 3, 3, 2, 5>, policy stacked_small, order 0, an odd number of 65..79 rows.  L.kodd stays false for
-                    // rtc > 0, so run_stacked launches the row's 16-byte base instance on those odd tables, as it always did.
-                    if (!even && !k.odd) {
-                        bool sibling_odd = false;
-                        for (const StackedShape& o : kStackedShapes)
-                            sibling_odd = sibling_odd || (k.rtc > 0 && o.rtc == 0 && o.odd && o.sd == k.sd && o.n == k.n && o.ct == k.ct && o.g == k.g);
-                        if (!sibling_odd) continue;
-                    }
-                    if (!holds_request(k, npts) || tighter_instance(k) || !fills_tiles(k, npts)) continue;
-                }
-                if (!k.matches(e->prog)) continue;
-                int rc = ensure_stacked(ctx, const_cast<fx_element*>(e), order);
-                if (rc != FX_OK) return rc;
-                if (e->stack_state[order] != 1) continue;
-                fxk::StackedArgs<0>& ka = L.khead;
-                memset(&ka, 0, sizeof ka);
-                L.fcoef.resize(e->prog.steps.size() * 3);
-                for (size_t q = 0; q < e->prog.steps.size(); ++q) {
-                    L.fcoef[3 * q + 0] = e->prog.steps[q].A;
-                    L.fcoef[3 * q + 1] = e->prog.steps[q].B;
-                    L.fcoef[3 * q + 2] = e->prog.steps[q].C;
-                }
-                ka.pts = pts;
-                ka.verts = verts;
-                ka.out = out;
-                const bool dofmajor = inmix || wg_mix1;
-                ka.afrag = pio ? e->d_astack_dmp[order] : dofmajor ? e->d_astack_dm[order] : e->d_astack[order];
-                if (!ka.afrag) continue;
-                if (pio) {
-                    for (int q = 0; q < 9; ++q) ka.G[q] = 0.5 * e->A0[q];
-                    ka.piola = mapping;
-                }
-                if (dofmajor && !invert_small(e->sd, e->A0, ka.A0inv)) continue;
-                ka.phi0 = e->prog.phi0;
-                memcpy(ka.A0, e->A0, sizeof ka.A0);
-                memcpy(ka.b0, e->b0, sizeof ka.b0);
-                ka.nreq = nreq;
-                ka.npts = npts;
-                ka.R = (int)R;
-                ka.RT = RT;
-                ka.debug = a.debug;
-                ka.lim_pts = (long long)nreq * npts * e->sd;
-                ka.lim_verts = verts ? (long long)nreq * (e->sd + 1) * e->sd : 0;
-                ka.lim_out = (long long)nreq * R * npts;
-                const int TRk = fxk::stacked_tile_rows(e->sd, pio ? 1 : 0);
-                ka.lim_afrag = (dofmajor ? ((long long)((rows + TRk - 1) / TRk) * ntab + 1) : (long long)(RT + 1)) * ((e->nexp + 3) / 4) * 64;
-                const bool mixr = pio || mix_odd || k.mixr;  // of the twin run_stacked will take
-                const int slots = fxk::stacked_mix_slots(e->sd, dofmajor ? ntab : 0, mixr);
-                L.klds_bytes = (fxk::WQ_CTL_DOUBLES + STACKED_NW * (fxk::stacked_image_doubles(k.ct, (e->nexp + 3) / 4, slots) + (mixr ? fxk::STACKED_KBUF : 0))) * 8;
-                if (wgk) {
-                    L.klds_bytes = fxwg::lds_bytes(k.sd, k.n, wg_ctw);
-                    L.wg_ct = wg_ctw;
-                    L.wg_mix = wg_mix1 ? 1 : 0;
-                    ka.gslab = wg_g;
-                }
-                if (L.klds_bytes > ctx->lds_per_cu) continue;
-                const long long groups = wgk ? ((nreq + wg_g - 1) / wg_g) * STACKED_NW : chunked ? nreq * ((npts + 16 * k.ct - 1) / (16 * k.ct)) : (nreq + k.g - 1) / k.g;
-                // one workgroup per CU = one wave per SIMD (measured: a second wave per SIMD at half the registers
-                // spills in the production phase and gains nothing, 1.45 -> 1.48 ms: the kernel is bound by the
-                // shared fp64 MFMA/VALU pipe, not by latencies)
-                // (the request-per-workgroup kernel's one-row-tile instances -- values-only requests of up to 64 rows -- are the
-                // exception: 256 registers, two workgroups a CU, 320 -> 298 us for degree-5 tetrahedra at 74 points)
-                const int wgs = wgk ? fxwg::workgroups_per_cu(k.sd, k.n, wg_ctw, wg_odd, wg_mix1 ? 1 : 0, RT) : 1;
-                L.kgrid = (int)std::max<long long>(1, std::min<long long>((groups + STACKED_NW - 1) / STACKED_NW, (long long)ctx->num_cu * wgs));
-                L.ncu = ctx->num_cu;
-                L.trash = ctx->d_trash;
-                L.ctx = ctx;
-                L.kmix_order = order;
-                L.kodd = wgk ? wg_odd : ((k.rtc == 0 && !even) || mix_odd);
-                L.kpiola = pio ? mapping : 0;
-                if (pio) L.fused_mapping = true;
-                L.stacked_id = (int)i;
-                L.small_id = -1;
-                if (fixed_yields) L.fixed_id = -1;
-                break;
-            }
-        }
-    }
-    int per_cu = std::max(1, std::min(16, ctx->lds_per_cu / std::max(1, L.lds_bytes)));
-    long long want = (long long)ctx->num_cu * per_cu * 4;
-    L.grid = (int)std::max<long long>(1, std::min<long long>(a.nitems, want));
-    return FX_OK;
-}
-
-int run_tabulate(fx_ctx* ctx, const fx_element* e, int order, const Launch& L, hipStream_t s) {
-    if (L.args.nitems == 0 || L.args.npts == 0) return FX_OK;
-    if (L.fixed_id >= 0) return run_fixed(L, s);
-    if (L.stacked_id >= 0) return run_stacked(L, s);
-    if (L.coop_id >= 0) return run_coop(L, s);
-    if (L.small_id >= 0) return run_small(order, L, s);
-    switch (e->sd) {
-        case 1: return launch_sd<1>(order, L, s);
-        case 2: return launch_sd<2>(order, L, s);
-        case 3: return launch_sd<3>(order, L, s);
-    }
-    return fail(FX_EINVAL, "Invalid number of spatial dimensions");
+    char tail[64];
+    snprintf(tail, sizeof tail, " fused_mapping=%d hash=%016llx", (int)L.fused_mapping, f.h);
+    return std::string(buf) + tail;
 }
 
 }  // namespace
@@ -2337,8 +1728,7 @@ int fx_tabulate_batch_shared(fx_ctx* ctx, const fx_element* e, int mapping, int 
     if (need <= (e->sd == 2 ? 3072u : 2048u) && !(ctx->policy & FX_POLICY_NO_SMALL) && !(scalar_values && !(e->sd == 2 && e->n >= 2)) && e->sd >= 2) {
         Launch L;
         const int prc = plan_launch(ctx, e, order, nreq, npts, ref_pts, verts, out, L, mapping);
-        if (prc == FX_OK && L.small_id >= 0 && L.fixed_id < 0 && L.stacked_id < 0 && L.coop_id < 0 &&
-            (mapping == FX_MAP_AFFINE || L.fused_mapping)) {
+        if (prc == FX_OK && L.winner == Family::Small && (mapping == FX_MAP_AFFINE || L.fused_mapping)) {
             L.sargs.shared_pts = 1;
             return run_small(order, L, s);
         }
@@ -2470,24 +1860,35 @@ int fx_plan_kernel(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, in
     static double dummy;
     int rc = plan_launch(ctx, e, order, nreq, npts, &dummy, (has_verts & 1) ? &dummy : nullptr, &dummy, L, (has_verts >> 2) & 3);
     if (rc != FX_OK) return rc;
-    if ((has_verts & 2) && L.stacked_id >= 0 && L.fixed_id < 0) {  // with the instance of the stacked-matrix registry
-        const StackedShape& k = kStackedShapes[L.stacked_id];
-        if (k.rtc == -7) snprintf(name, (size_t)name_len, "fxk::tabulate_simplex_wg<%d,%d,%d>%s", k.sd, k.n, L.wg_ct,
+    std::string report;
+    if ((has_verts & 2) && L.winner == Family::Stacked) {  // with the instance of the stacked-matrix registry
+        const StackedShape& k = kStackedShapes[L.row];
+        char buf[96];
+        if (k.rtc == -7) snprintf(buf, sizeof buf, "fxk::tabulate_simplex_wg<%d,%d,%d>%s", k.sd, k.n, L.wg_ct,
                                   ((L.khead.gslab > 1 ? "x" + std::to_string(L.khead.gslab) : std::string()) + (L.wg_mix ? "+mix" : "")).c_str());
-        else snprintf(name, (size_t)name_len, "fxk::tabulate_simplex_stacked<%d,%d,%d,%d,%d>%s", k.sd, k.n, k.ct, k.g, k.rtc,
+        else snprintf(buf, sizeof buf, "fxk::tabulate_simplex_stacked<%d,%d,%d,%d,%d>%s", k.sd, k.n, k.ct, k.g, k.rtc,
                       L.kpiola ? "+piola" : "");
-        return FX_OK;
+        report = buf;
+    } else {
+        switch (L.winner) {
+            case Family::Fixed:
+                report = L.fkind == 0 ? "fxk::tabulate_simplex_fixed" : L.fkind == 1 ? "fxk::tabulate_simplex_stream" : "fxk::tabulate_simplex_pair";
+                break;
+            case Family::Stacked:
+                report = kStackedShapes[L.row].rtc == -7 ? "fxk::tabulate_simplex_wg" : "fxk::tabulate_simplex_stacked";
+                break;
+            case Family::Coop: report = "fxk::tabulate_simplex_coop"; break;
+            case Family::Small: report = "fxk::tabulate_simplex_small"; break;
+            case Family::Generic:
+            case Family::None: report = "fxk::tabulate_simplex_kernel"; break;
+        }
     }
-    const char* k = "fxk::tabulate_simplex_kernel";
-    if (L.fixed_id >= 0)
-        k = L.fkind == 0   ? "fxk::tabulate_simplex_fixed"
-            : L.fkind == 1 ? "fxk::tabulate_simplex_stream"
-                           : "fxk::tabulate_simplex_pair";
-    else if (L.stacked_id >= 0)
-        k = kStackedShapes[L.stacked_id].rtc == -7 ? "fxk::tabulate_simplex_wg" : "fxk::tabulate_simplex_stacked";
-    else if (L.coop_id >= 0) k = "fxk::tabulate_simplex_coop";
-    else if (L.small_id >= 0) k = "fxk::tabulate_simplex_small";
-    snprintf(name, (size_t)name_len, "%s", k);
+    if (has_verts & 16) {  // (tools/route_sweep.py --digest; no blank inside a report)
+        std::string d = plan_digest(L, e, order);
+        std::replace(d.begin(), d.end(), ' ', ',');
+        report += "{" + d + "}";
+    }
+    snprintf(name, (size_t)name_len, "%s", report.c_str());
     return FX_OK;
 }
 

@@ -218,13 +218,16 @@ class SimplexPolySet:
                                            _dev_ptr(ref_pts), _dev_ptr(verts), _dev_ptr(out), _stream_ptr(stream)))
         return out
 
-    def kernel_name(self, order, nreq, npts, has_verts=False, instance=False, mapping=None):
+    def kernel_name(self, order, nreq, npts, has_verts=False, instance=False, mapping=None, digest=False):
         """Device kernel ``tabulate_batch`` launches for this request shape (fx_plan_kernel); ``instance``: with the
-        registry instance of the stacked-matrix kernel; ``mapping``: the Piola map asked for with the tabulation."""
-        buf = ctypes.create_string_buffer(96)
+        registry instance of the stacked-matrix kernel; ``mapping``: the Piola map asked for with the tabulation;
+        ``digest``: followed by ``{...}``, the planned launch itself -- family, registry row, grid, LDS bytes, every
+        integer the launcher reads and a hash of the floating-point arguments."""
+        size = 1024 if digest else 96
+        buf = ctypes.create_string_buffer(size)
         code = self.MAPPINGS[mapping] if mapping else 0
-        flags = int(bool(has_verts)) | (2 if instance else 0) | ((code << 2) if code in (1, 2) else 0)
-        check(lib.fx_plan_kernel(self.ctx.handle, self.handle, int(order), int(nreq), int(npts), flags, buf, 96))
+        flags = int(bool(has_verts)) | (2 if instance else 0) | ((code << 2) if code in (1, 2) else 0) | (16 if digest else 0)
+        check(lib.fx_plan_kernel(self.ctx.handle, self.handle, int(order), int(nreq), int(npts), flags, buf, size))
         return buf.value.decode()
 
     def time_tabulate_batch(self, order, pts, verts, out, reps, stream=None):
