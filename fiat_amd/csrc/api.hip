@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/fiat_amd.h"
+#include "host_common.hpp"  // fail, FX_HIP_TRY, DeviceBuffer, StreamScratch
 #include "aux_kernels.hpp"
 #include "plan.hpp"
 #include "simplex_kernel.hpp"
@@ -45,25 +47,6 @@ inline const char* ab_env(const char*) { return nullptr; }
 #endif
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (void)hipGetLastError(); /* reported here: not again by the next launch check */ \
-            return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));                  \
-        }                                                                                  \
-    } while (0)
 
 const double UFC[3][12] = {
     {0.0, 1.0},
@@ -158,10 +141,10 @@ struct fx_ctx {
     int num_cu = 0;
     int lds_per_cu = 0;
     std::string name;
-    double* d_trash = nullptr;  // 64 KB scratch (ablation builds: wave lifetimes, FX_DBG & 512)
+    DeviceBuffer<double> d_trash;  // 64 KB scratch (ablation builds: wave lifetimes, FX_DBG & 512)
     // chunk counters of the dynamically scheduled kernels (work_queue.hpp), 128 B apart, in blocks of CounterHandout::BLOCK
     // that are added as streams and captures appear and live as long as the context (counter_handout.hpp)
-    std::vector<unsigned long long*> queue_blocks;
+    std::vector<DeviceBuffer<unsigned long long>> queue_blocks;
     fx::CounterHandout counters;
     unsigned policy = 0;      // FX_POLICY_* bits (fx_ctx_set_policy)
 };
@@ -169,13 +152,9 @@ struct fx_ctx {
 namespace {
 bool grow_counters(fx_ctx* ctx, int first, int count) {
     if (first != (int)ctx->queue_blocks.size() * fx::CounterHandout::BLOCK || count != fx::CounterHandout::BLOCK) return false;
-    unsigned long long* p = nullptr;
-    if (hipMalloc(&p, (size_t)count * 128) != hipSuccess || hipMemset(p, 0, (size_t)count * 128) != hipSuccess) {
-        (void)hipGetLastError();
-        if (p) (void)hipFree(p);
-        return false;
-    }
-    ctx->queue_blocks.push_back(p);
+    DeviceBuffer<unsigned long long> block;
+    if (block.alloc((size_t)count * 16, true) != hipSuccess) return false;  // (128 B per counter)
+    ctx->queue_blocks.push_back(std::move(block));
     return true;
 }
 
@@ -205,7 +184,7 @@ unsigned int* work_counter(fx_ctx* ctx, hipStream_t s) {
         fail(FX_ENOMEM, "out of device memory for the work counters of a new stream");
         return nullptr;
     }
-    return reinterpret_cast<unsigned int*>(ctx->queue_blocks[idx / fx::CounterHandout::BLOCK] + (size_t)(idx % fx::CounterHandout::BLOCK) * 16);
+    return reinterpret_cast<unsigned int*>(ctx->queue_blocks[idx / fx::CounterHandout::BLOCK].get() + (size_t)(idx % fx::CounterHandout::BLOCK) * 16);
 }
 }  // namespace
 
@@ -237,35 +216,35 @@ struct fx_element {
     fx::Program prog;
     std::vector<double> T;  // C0 transform (bubble) or empty
     int KS = 0, MT = 0;
-    fxk::Step* d_steps = nullptr;
-    double* d_afrag = nullptr;
-    double* d_cmat = nullptr;          // plain coefficient matrix [rows][nexp] (C0 transform folded in)
-    double* d_afrag_split = nullptr;  // layout of the shape-specialised kernels
-    double* d_afrag_stream = nullptr; // same, K in production order (K-streamed kernel)
+    DeviceBuffer<fxk::Step> d_steps;
+    DeviceBuffer<double> d_afrag;
+    DeviceBuffer<double> d_cmat;          // plain coefficient matrix [rows][nexp] (C0 transform folded in)
+    DeviceBuffer<double> d_afrag_split;  // layout of the shape-specialised kernels
+    DeviceBuffer<double> d_afrag_stream; // same, K in production order (K-streamed kernel)
     // cooperative (large-shape) plan
     int coop_KS = 0, coop_emax = 0;
-    int* d_coop_eint = nullptr;
-    double* d_coop_edbl = nullptr;
-    int* d_coop_kstart = nullptr;
-    double* d_afrag_coop = nullptr;
+    DeviceBuffer<int> d_coop_eint;
+    DeviceBuffer<double> d_coop_edbl;
+    DeviceBuffer<int> d_coop_kstart;
+    DeviceBuffer<double> d_afrag_coop;
     // stacked-matrix kernel (simplex_stacked.hpp): effective coefficients on the host, A fragments of
     // [C; C D^alpha ...] per derivative order (built at first use, ensure_stacked)
     std::vector<double> hC;
-    double* d_astack[3] = {nullptr, nullptr, nullptr};
-    double* d_astack_dm[3] = {nullptr, nullptr, nullptr};   // orders 1 and 2, dof-major tiles (the tables of 16 dofs one after the other, each padded to a tile): MIXT instances
-    double* d_astack_dmp[3] = {nullptr, nullptr, nullptr};  // orders 0-2, vector-valued elements: dof-major tiles with the components of a dof in one MFMA lane (PIO instances)
+    DeviceBuffer<double> d_astack[3];
+    DeviceBuffer<double> d_astack_dm[3];   // orders 1 and 2, dof-major tiles (the tables of 16 dofs one after the other, each padded to a tile): MIXT instances
+    DeviceBuffer<double> d_astack_dmp[3];  // orders 0-2, vector-valued elements: dof-major tiles with the components of a dof in one MFMA lane (PIO instances)
     int stack_state[3] = {0, 0, 0};  // 0 not built, 1 built, -1 failed
     bool raw_expansion = false;      // internal helper element (identity coefficients): never takes the stacked path
     // derivative orders 3..FX_MAX_ORDER (ensure_high_order): an internal element whose rows are the stacked matrix
     // [C D^alpha], |alpha| <= order, tabulated at order 0
-    fx_element* high[FX_MAX_ORDER + 1] = {nullptr};
+    std::unique_ptr<fx_element> high[FX_MAX_ORDER + 1];
     int high_state[FX_MAX_ORDER + 1] = {0};
 };
 
 struct fx_line_element {
     fx_ctx* ctx = nullptr;
     int nn = 0;
-    double* d_buf = nullptr;  // nodes | wts | dmat
+    DeviceBuffer<double> d_buf;  // nodes | wts | dmat
     std::vector<double> nodes, wts, dmat;
 };
 
@@ -287,10 +266,11 @@ int fx_ctx_create(int device_id, fx_ctx** out) {
         return fail(FX_EHIP, "fx_ctx_create: no HIP device available (%s); fiat_amd has no CPU fallback",
                     e == hipSuccess ? "device count 0" : hipGetErrorString(e));
     if (device_id < 0 || device_id >= count) return fail(FX_EINVAL, "fx_ctx_create: device %d out of range", device_id);
-    HIP_TRY(hipSetDevice(device_id));
+    FX_HIP_TRY(hipSetDevice(device_id));
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    fx_ctx* c = new fx_ctx;
+    FX_HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    std::unique_ptr<fx_ctx> owner(new fx_ctx);  // (a failed create releases what it and counters.reserve allocated)
+    fx_ctx* c = owner.get();
     c->device = device_id;
     c->num_cu = prop.multiProcessorCount;
     c->lds_per_cu = (int)prop.maxSharedMemoryPerMultiProcessor;
@@ -301,20 +281,14 @@ int fx_ctx_create(int device_id, fx_ctx** out) {
 #else
     const size_t trash_bytes = 64 * 1024;
 #endif
-    if (hipMalloc(&c->d_trash, trash_bytes) != hipSuccess ||
-        !c->counters.reserve([c](int first, int count) { return grow_counters(c, first, count); })) {
-        if (c->d_trash) (void)hipFree(c->d_trash);
-        delete c;
+    if (c->d_trash.alloc(trash_bytes / sizeof(double)) != hipSuccess ||
+        !c->counters.reserve([c](int first, int count) { return grow_counters(c, first, count); }))
         return fail(FX_ENOMEM, "fx_ctx_create: out of device memory");
-    }
-    *out = c;
+    *out = owner.release();
     return FX_OK;
 }
 
 int fx_ctx_destroy(fx_ctx* ctx) {
-    if (ctx && ctx->d_trash) (void)hipFree(ctx->d_trash);
-    if (ctx)
-        for (unsigned long long* p : ctx->queue_blocks) (void)hipFree(p);
     delete ctx;
     return FX_OK;
 }
@@ -427,52 +401,20 @@ static int upload_coeffs(fx_element* e, int ndof, int vdim, const double* coeffs
             }
         C.swap(CT);
     }
-    e->hC = C;
-    for (int o = 0; o < 3; ++o) {
-        if (e->d_astack[o]) (void)hipFree(e->d_astack[o]);
-        e->d_astack[o] = nullptr;
-        e->stack_state[o] = 0;
-    }
-    for (int o = 0; o < 3; ++o) {
-        if (e->d_astack_dm[o]) (void)hipFree(e->d_astack_dm[o]);
-        e->d_astack_dm[o] = nullptr;
-        if (e->d_astack_dmp[o]) (void)hipFree(e->d_astack_dmp[o]);
-        e->d_astack_dmp[o] = nullptr;
-    }
-    for (int o = 0; o <= FX_MAX_ORDER; ++o) {
-        if (e->high[o]) fx_element_destroy(e->high[o]);
-        e->high[o] = nullptr;
-        e->high_state[o] = 0;
-    }
-    if (e->d_cmat) {
-        HIP_TRY(hipFree(e->d_cmat));
-        e->d_cmat = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_cmat, C.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_cmat, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice));
+    // build-then-commit (device_buffer.hpp): every new buffer and derived value in locals first, so that a failure returns with
+    // the element as it was
+    DeviceBuffer<double> d_cmat, d_afrag, d_afrag_split, d_afrag_stream, d_afrag_coop, d_coop_edbl;
+    DeviceBuffer<int> d_coop_eint, d_coop_kstart;
+    int coop_KS = e->coop_KS, coop_emax = e->coop_emax;
+    FX_HIP_TRY(d_cmat.upload(C.data(), C.size()));
     std::vector<double> F = fx::pack_a_fragments(C, rows, nexp);
-    if (e->d_afrag) {
-        HIP_TRY(hipFree(e->d_afrag));
-        e->d_afrag = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_afrag, F.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_afrag, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice));
+    FX_HIP_TRY(d_afrag.upload(F.data(), F.size()));
     std::vector<double> F2 = fx::pack_a_fragments_split(C, rows, nexp);
-    if (e->d_afrag_split) {
-        HIP_TRY(hipFree(e->d_afrag_split));
-        e->d_afrag_split = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_afrag_split, F2.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_afrag_split, F2.data(), F2.size() * sizeof(double), hipMemcpyHostToDevice));
+    FX_HIP_TRY(d_afrag_split.upload(F2.data(), F2.size()));
     std::vector<int> kperm(nexp, 0);
     for (size_t i = 0; i < e->prog.steps.size() && (int)i + 1 < nexp; ++i) kperm[i + 1] = e->prog.steps[i].dst;
     std::vector<double> F3 = fx::pack_a_fragments_split(C, rows, nexp, &kperm);
-    if (e->d_afrag_stream) {
-        HIP_TRY(hipFree(e->d_afrag_stream));
-        e->d_afrag_stream = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_afrag_stream, F3.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_afrag_stream, F3.data(), F3.size() * sizeof(double), hipMemcpyHostToDevice));
+    FX_HIP_TRY(d_afrag_stream.upload(F3.data(), F3.size()));
     if (e->n >= 1) {
         // cooperative plan: entry tables of the four producers + A fragments in slot order
         fx::CoopPlan cp = fx::build_coop_plan(e->prog);
@@ -516,27 +458,61 @@ static int upload_coeffs(fx_element* e, int ndof, int vdim, const double* coeffs
             for (int j = 0; j <= cp.KS; ++j) kst[(size_t)w * (cp.KS + 1) + j] = cp.kstart[w][j];
         }
         std::vector<double> F4 = fx::pack_a_fragments_split(C, rows, nexp, &cp.kperm);
-        auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-            if (*dst) {
-                (void)hipFree(*dst);
-                *dst = nullptr;
-            }
-            hipError_t he = hipMalloc(dst, bytes);
-            if (he == hipSuccess) he = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-            return he;
-        };
-        HIP_TRY(upload((void**)&e->d_coop_eint, eint.data(), eint.size() * sizeof(int)));
-        HIP_TRY(upload((void**)&e->d_coop_edbl, edbl.data(), edbl.size() * sizeof(double)));
-        HIP_TRY(upload((void**)&e->d_coop_kstart, kst.data(), kst.size() * sizeof(int)));
-        HIP_TRY(upload((void**)&e->d_afrag_coop, F4.data(), F4.size() * sizeof(double)));
-        e->coop_KS = cp.KS;
-        e->coop_emax = emax;
+        FX_HIP_TRY(d_coop_eint.upload(eint.data(), eint.size()));
+        FX_HIP_TRY(d_coop_edbl.upload(edbl.data(), edbl.size()));
+        FX_HIP_TRY(d_coop_kstart.upload(kst.data(), kst.size()));
+        FX_HIP_TRY(d_afrag_coop.upload(F4.data(), F4.size()));
+        coop_KS = cp.KS;
+        coop_emax = emax;
+    }
+    // commit: nothing below can fail.  The old buffers go as the new ones move in; what was built from the old coefficients
+    // (stacked matrices, the internal elements of orders > 2) is dropped.
+    e->hC.swap(C);
+    e->d_cmat = std::move(d_cmat);
+    e->d_afrag = std::move(d_afrag);
+    e->d_afrag_split = std::move(d_afrag_split);
+    e->d_afrag_stream = std::move(d_afrag_stream);
+    e->d_coop_eint = std::move(d_coop_eint);  // (degree 0: no cooperative plan, before or after)
+    e->d_coop_edbl = std::move(d_coop_edbl);
+    e->d_coop_kstart = std::move(d_coop_kstart);
+    e->d_afrag_coop = std::move(d_afrag_coop);
+    e->coop_KS = coop_KS;
+    e->coop_emax = coop_emax;
+    for (int o = 0; o < 3; ++o) {
+        (void)e->d_astack[o].reset();
+        (void)e->d_astack_dm[o].reset();
+        (void)e->d_astack_dmp[o].reset();
+        e->stack_state[o] = 0;
+    }
+    for (int o = 0; o <= FX_MAX_ORDER; ++o) {
+        e->high[o].reset();
+        e->high_state[o] = 0;
     }
     e->ndof = ndof;
     e->vdim = vdim;
     e->MT = (rows + 15) / 16;
     e->KS = (nexp + 3) / 4;
     return FX_OK;
+}
+
+// An element without coefficients: the expansion set (sd, n, variant, scale) on the cell of (A0, b0), with its step table on the
+// device.  fx_element_create and the internal elements (project_derivative_matrices, ensure_high_order) start from it.
+static hipError_t make_element_shell(fx_ctx* ctx, int sd, int n, int variant, double scale, const double* A0, const double* b0,
+                                     fx::Program prog, std::unique_ptr<fx_element>& out) {
+    static_assert(sizeof(fx::Step) == sizeof(fxk::Step), "step layout");
+    std::unique_ptr<fx_element> e(new fx_element);
+    e->ctx = ctx;
+    e->sd = sd;
+    e->n = n;
+    e->variant = variant;
+    e->nexp = fx::binom(n + sd, sd);
+    e->scale = scale;
+    memcpy(e->A0, A0, sizeof e->A0);
+    memcpy(e->b0, b0, sizeof e->b0);
+    e->prog = std::move(prog);
+    const hipError_t he = e->d_steps.upload(reinterpret_cast<const fxk::Step*>(e->prog.steps.data()), e->prog.steps.size(), 1);
+    if (he == hipSuccess) out = std::move(e);
+    return he;
 }
 
 int fx_element_create(fx_ctx* ctx, int sd, int n, int variant, double scale, const double* verts,
@@ -547,68 +523,31 @@ int fx_element_create(fx_ctx* ctx, int sd, int n, int variant, double scale, con
     if (variant < 0 || variant > 2) return fail(FX_EINVAL, "Invalid variant %d", variant);
     if (variant == FX_VARIANT_BUBBLE && n < 1) return fail(FX_EINVAL, "bubble variant needs degree >= 1");
     if (ndof < 1 || vdim < 1) return fail(FX_EINVAL, "bad ndof/vdim");
-    HIP_TRY(hipSetDevice(ctx->device));
-    fx_element* e = new fx_element;
-    e->ctx = ctx;
-    e->sd = sd;
-    e->n = n;
-    e->variant = variant;
-    e->nexp = fx::binom(n + sd, sd);
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     if (scale <= 0.0) {
         scale = std::sqrt(1.0 / default_simplex_volume(sd));
         if (n == 0 && sd > 1) scale = 1.0;  // expansions.py:396-398
     }
-    e->scale = scale;
-    if (!host_cell_map(sd, verts ? verts : UFC[sd - 1], e->A0, e->b0)) {
-        delete e;
-        return fail(FX_EINVAL, "degenerate cell");
-    }
-    e->prog = fx::build_program(sd, n, variant, scale);
+    double A0[9] = {0}, b0[3] = {0};
+    if (!host_cell_map(sd, verts ? verts : UFC[sd - 1], A0, b0)) return fail(FX_EINVAL, "degenerate cell");
+    std::unique_ptr<fx_element> e;
+    const hipError_t he = make_element_shell(ctx, sd, n, variant, scale, A0, b0, fx::build_program(sd, n, variant, scale), e);
+    if (he != hipSuccess) return fail(FX_EHIP, "fx_element_create: %s", hipGetErrorString(he));
     if (variant == FX_VARIANT_BUBBLE) e->T = fx::c0_transform(sd, n);
-    static_assert(sizeof(fx::Step) == sizeof(fxk::Step), "step layout");
-    size_t sbytes = std::max<size_t>(1, e->prog.steps.size()) * sizeof(fxk::Step);
-    hipError_t he = hipMalloc(&e->d_steps, sbytes);
-    if (he == hipSuccess && !e->prog.steps.empty())
-        he = hipMemcpy(e->d_steps, e->prog.steps.data(), e->prog.steps.size() * sizeof(fxk::Step), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        fx_element_destroy(e);
-        return fail(FX_EHIP, "fx_element_create: %s", hipGetErrorString(he));
-    }
-    int rc = upload_coeffs(e, ndof, vdim, coeffs);
-    if (rc != FX_OK) {
-        fx_element_destroy(e);
-        return rc;
-    }
-    *out = e;
+    const int rc = upload_coeffs(e.get(), ndof, vdim, coeffs);
+    if (rc != FX_OK) return rc;
+    *out = e.release();
     return FX_OK;
 }
 
 int fx_element_destroy(fx_element* e) {
-    if (!e) return FX_OK;
-    if (e->d_steps) (void)hipFree(e->d_steps);
-    if (e->d_cmat) (void)hipFree(e->d_cmat);
-    if (e->d_afrag) (void)hipFree(e->d_afrag);
-    if (e->d_afrag_split) (void)hipFree(e->d_afrag_split);
-    if (e->d_afrag_stream) (void)hipFree(e->d_afrag_stream);
-    if (e->d_coop_eint) (void)hipFree(e->d_coop_eint);
-    if (e->d_coop_edbl) (void)hipFree(e->d_coop_edbl);
-    if (e->d_coop_kstart) (void)hipFree(e->d_coop_kstart);
-    if (e->d_afrag_coop) (void)hipFree(e->d_afrag_coop);
-    for (int o = 0; o < 3; ++o)
-        if (e->d_astack[o]) (void)hipFree(e->d_astack[o]);
-    for (int o = 0; o < 3; ++o) {
-        if (e->d_astack_dm[o]) (void)hipFree(e->d_astack_dm[o]);
-        if (e->d_astack_dmp[o]) (void)hipFree(e->d_astack_dmp[o]);
-    }
-    for (int o = 0; o <= FX_MAX_ORDER; ++o)
-        if (e->high[o]) fx_element_destroy(e->high[o]);
     delete e;
     return FX_OK;
 }
 
 int fx_element_set_coeffs(fx_element* e, int ndof, int vdim, const double* coeffs) {
     if (!e || ndof < 1 || vdim < 1) return fail(FX_EINVAL, "fx_element_set_coeffs: bad argument");
-    HIP_TRY(hipSetDevice(e->ctx->device));
+    FX_HIP_TRY(hipSetDevice(e->ctx->device));
     return upload_coeffs(e, ndof, vdim, coeffs);
 }
 
@@ -800,9 +739,9 @@ int launch_fixed(const Launch& L, hipStream_t s) {
         static thread_local int cached_lds = -1, cached_occ = 0;
         if (cached_kp != reinterpret_cast<const void*>(kp) || cached_lds != lds_bytes) {
             if (lds_bytes > 48 * 1024)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+                FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
             int q = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kp), 64 * PAIR_NW, (size_t)lds_bytes));
+            FX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kp), 64 * PAIR_NW, (size_t)lds_bytes));
             cached_kp = reinterpret_cast<const void*>(kp);
             cached_lds = lds_bytes;
             cached_occ = q;
@@ -831,9 +770,9 @@ int launch_fixed(const Launch& L, hipStream_t s) {
         unsigned int* const counter = work_counter(L.ctx, s);
         if (!counter) return FX_ENOMEM;
         hipLaunchKernelGGL(kp, dim3(grid), dim3(64 * PAIR_NW), lds_bytes, s, fa, L.trash, counter);
-        HIP_TRY(hipGetLastError());
+        FX_HIP_TRY(hipGetLastError());
 #if defined(FX_DBG) && (FX_DBG & 512)
-        if (verbose) HIP_TRY(report_wave_lifetimes(L.trash, grid, PAIR_NW));
+        if (verbose) FX_HIP_TRY(report_wave_lifetimes(L.trash, grid, PAIR_NW));
 #endif
         return FX_OK;
     }
@@ -847,11 +786,11 @@ int launch_fixed(const Launch& L, hipStream_t s) {
         else
             kern = (KernT)fxk::tabulate_simplex_fixed<SD, N, ORDER, ROWS, NT, FIXED_NW>;
         if (L.flds_bytes > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+            FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         L.flds_bytes));
         const int grid = L.fgrid;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * FIXED_NW), L.flds_bytes, s, fa);
-        HIP_TRY(hipGetLastError());
+        FX_HIP_TRY(hipGetLastError());
         return FX_OK;
     }
 }
@@ -933,7 +872,7 @@ int stacked_mix_pass(const Launch& L, hipStream_t s) {
         if ((long long)fxk::MIX_RB * ma.n > 0x3fffffffLL) return fail(FX_EINVAL, "request too large for the table-mixing pass");
         const long long blocks = ma.rb > 1 ? std::min<long long>((L.khead.nreq + ma.rb - 1) / ma.rb, (long long)L.ncu * 16) : L.khead.nreq * ma.slices;
         hipLaunchKernelGGL((fxk::table_mix_kernel<SD>), dim3((unsigned)std::max<long long>(1, blocks)), dim3(256), 0, s, ma);
-        HIP_TRY(hipGetLastError());
+        FX_HIP_TRY(hipGetLastError());
     }
     return FX_OK;
 }
@@ -969,9 +908,9 @@ int launch_stacked(const Launch& L, hipStream_t s) {
     static thread_local int occ = 0;
     if (occ == 0) {
         if (L.klds_bytes > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.klds_bytes));
+            FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.klds_bytes));
         int q = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kern), 64 * STACKED_NW, (size_t)L.klds_bytes));
+        FX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void*>(kern), 64 * STACKED_NW, (size_t)L.klds_bytes));
         occ = std::max(1, q);
         static const int cap = ab_env("FIAT_AMD_STACKED_WPS") ? atoi(ab_env("FIAT_AMD_STACKED_WPS")) : 8;
         occ = std::min(occ, std::max(1, cap));
@@ -982,15 +921,15 @@ int launch_stacked(const Launch& L, hipStream_t s) {
     unsigned int* const counter = work_counter(L.ctx, s);
     if (!counter) return FX_ENOMEM;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * STACKED_NW), L.klds_bytes, s, ka, L.trash, counter);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
 #if defined(FX_DBG) && (FX_DBG & 512)
-    if (ab_env("FIAT_AMD_VERBOSE")) HIP_TRY(report_wave_lifetimes(L.trash, grid, STACKED_NW));
+    if (ab_env("FIAT_AMD_VERBOSE")) FX_HIP_TRY(report_wave_lifetimes(L.trash, grid, STACKED_NW));
 #endif
 #if defined(FX_DBG) && (FX_DBG & 1024)
     {   // range-check build: report accesses that left their buffers (redirected to the scratch area by the kernel)
         double rep[20];
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(rep, L.trash + 4096, sizeof rep, hipMemcpyDeviceToHost));
+        FX_HIP_TRY(hipDeviceSynchronize());
+        FX_HIP_TRY(hipMemcpy(rep, L.trash + 4096, sizeof rep, hipMemcpyDeviceToHost));
         static const char* site[] = {"", "pts", "verts", "afrag", "out"};
         for (int k = 1; k <= 4; ++k) {
             unsigned long long cnt;
@@ -999,7 +938,7 @@ int launch_stacked(const Launch& L, hipStream_t s) {
                 fprintf(stderr, "[fiat_amd] RANGE CHECK <%d,%d,%d,%d,mixt %d>: %llu accesses outside `%s`: first index %.0f, limit %.0f, group %.0f\n",
                         SD, N, CT, G, MIXT, cnt, site[k], rep[4 * k + 1], rep[4 * k + 2], rep[4 * k + 3]);
         }
-        HIP_TRY(hipMemset(L.trash + 4096, 0, sizeof rep));
+        FX_HIP_TRY(hipMemset(L.trash + 4096, 0, sizeof rep));
         if (ab_env("FIAT_AMD_VERBOSE")) fprintf(stderr, "[fiat_amd] range check done <%d,%d,%d,%d,mixt %d>\n", SD, N, CT, G, MIXT);
     }
 #endif
@@ -1191,10 +1130,10 @@ int launch_coop(const Launch& L, hipStream_t s) {
     }
     if (!kern) return fail(FX_EINVAL, "internal: this cooperative shape only fuses a push-forward");
     if (L.clds_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     L.clds_bytes));
     hipLaunchKernelGGL(kern, dim3(L.cgrid), dim3(512), L.clds_bytes, s, L.cargs);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1229,7 +1168,7 @@ template <int SD, int N>
 int launch_small_values(int order, const Launch& L, hipStream_t s) {
     if (order != 0 || L.sargs.piola) return fail(FX_EINVAL, "internal: unknown small kernel %d", L.row);
     hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 0, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1245,7 +1184,7 @@ int launch_small(int order, const Launch& L, hipStream_t s) {
                 hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 2, SMALL_NW, true>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
             else
                 return fail(FX_EINVAL, "internal: no fused push-forward for this lane-local shape");
-            HIP_TRY(hipGetLastError());
+            FX_HIP_TRY(hipGetLastError());
             return FX_OK;
         }
     }
@@ -1255,7 +1194,7 @@ int launch_small(int order, const Launch& L, hipStream_t s) {
         hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 1, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
     else
         hipLaunchKernelGGL((fxk::tabulate_simplex_small<SD, N, 2, SMALL_NW>), dim3(L.sgrid), dim3(64 * SMALL_NW), L.slds_bytes, s, L.sargs);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1293,11 +1232,11 @@ template <int SD, int ORDER, int KS_T, int MT_T>
 int launch_one(const Launch& L, hipStream_t s) {
     auto kern = fxk::tabulate_simplex_kernel<SD, ORDER, 1, KS_T, MT_T>;
     if (L.lds_bytes > 48 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     L.lds_bytes));
     }
     hipLaunchKernelGGL(kern, dim3(L.grid), dim3(64), L.lds_bytes, s, L.args);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1361,7 +1300,7 @@ std::string plan_digest(const Launch& L, const fx_element* e, int order) {
             snprintf(buf, sizeof buf,
                      "fam=generic grid=%d lds=%d verts=%d afrag=%s nreq=%lld nitems=%lld npts=%d rows=%d nexp=%d nsteps=%d KS=%d MT=%d "
                      "ntab=%d P=%d pc=%d nchunk=%d phi_doubles=%d stage_doubles=%d debug=%d",
-                     L.grid, L.lds_bytes, a.verts != nullptr, a.afrag == e->d_afrag ? "plain" : "?", a.nreq, a.nitems, a.npts,
+                     L.grid, L.lds_bytes, a.verts != nullptr, a.afrag == e->d_afrag.get() ? "plain" : "?", a.nreq, a.nitems, a.npts,
                      a.rows, a.nexp, a.nsteps, a.KS, a.MT, a.ntab, a.P, a.pc, a.nchunk, a.phi_doubles, a.stage_doubles, a.debug);
             break;
         }
@@ -1371,7 +1310,7 @@ std::string plan_digest(const Launch& L, const fx_element* e, int order) {
             snprintf(buf, sizeof buf,
                      "fam=coop row=%d grid=%d lds=%d verts=%d afrag=%s nreq=%lld npts=%d rows=%d KS=%d NT=%d emax=%d TR=%d "
                      "slab_doubles=%d img_doubles=%d debug=%d piola=%d",
-                     L.row, L.cgrid, L.clds_bytes, a.verts != nullptr, a.afrag == e->d_afrag_coop ? "coop" : "?", a.nreq,
+                     L.row, L.cgrid, L.clds_bytes, a.verts != nullptr, a.afrag == e->d_afrag_coop.get() ? "coop" : "?", a.nreq,
                      a.npts, a.rows, a.KS, a.NT, a.emax, a.TR, a.slab_doubles, a.img_doubles, a.debug, a.piola);
             break;
         }
@@ -1382,7 +1321,7 @@ std::string plan_digest(const Launch& L, const fx_element* e, int order) {
                      "fam=fixed row=%d fkind=%d grid=%d lds=%d ncu=%d verts=%d afrag=%s nreq=%lld npts=%d lds_doubles=%d debug=%d "
                      "ncoef=%d nucoef=%d",
                      L.row, L.fkind, L.fgrid, L.flds_bytes, L.ncu, a.verts != nullptr,
-                     a.afrag == e->d_afrag_stream ? "stream" : a.afrag == e->d_afrag_split ? "split" : "?", a.nreq, a.npts,
+                     a.afrag == e->d_afrag_stream.get() ? "stream" : a.afrag == e->d_afrag_split.get() ? "split" : "?", a.nreq, a.npts,
                      a.lds_doubles, a.debug, (int)L.fcoef.size(), (int)L.fucoef.size());
             break;
         }
@@ -1392,15 +1331,15 @@ std::string plan_digest(const Launch& L, const fx_element* e, int order) {
             snprintf(buf, sizeof buf,
                      "fam=small row=%d grid=%d lds=%d verts=%d afrag=%s nreq=%lld nitems=%lld npts=%d rows=%d P=%d stage_doubles=%d "
                      "debug=%d piola=%d shared_pts=%d",
-                     L.row, L.sgrid, L.slds_bytes, a.verts != nullptr, a.cmat == e->d_cmat ? "cmat" : "?", a.nreq, a.nitems,
+                     L.row, L.sgrid, L.slds_bytes, a.verts != nullptr, a.cmat == e->d_cmat.get() ? "cmat" : "?", a.nreq, a.nitems,
                      a.npts, a.rows, a.P, a.stage_doubles, a.debug, a.piola, a.shared_pts);
             break;
         }
         case Family::Stacked: {
             const fxk::StackedArgs<0>& a = L.khead;
             f.add(&a.phi0, 1), f.add(a.A0, 9), f.add(a.b0, 3), f.add(a.A0inv, 9), f.add(a.G, 9), f.add(L.fcoef.data(), L.fcoef.size());
-            const char* tab = a.afrag == e->d_astack_dmp[order] ? "dmp" : a.afrag == e->d_astack_dm[order] ? "dm"
-                              : a.afrag == e->d_astack[order]   ? "plain" : "?";
+            const char* tab = a.afrag == e->d_astack_dmp[order].get() ? "dmp" : a.afrag == e->d_astack_dm[order].get() ? "dm"
+                              : a.afrag == e->d_astack[order].get() ? "plain" : "?";
             snprintf(buf, sizeof buf,
                      "fam=stacked row=%d grid=%d lds=%d ncu=%d verts=%d afrag=%s nreq=%lld npts=%d R=%d RT=%d gslab=%d piola=%d debug=%d "
                      "lim_pts=%lld lim_verts=%lld lim_out=%lld lim_afrag=%lld kmix_order=%d kodd=%d kpiola=%d wg_ct=%d wg_mix=%d ncoef=%d",
@@ -1468,7 +1407,7 @@ int launch_shared(int order, const fxk::SharedArgs& sa, int ncu, hipStream_t s, 
                 case 1: hipLaunchKernelGGL((fxk::shared_points_flat_kernel<SD, 1>), dim3(fgrid), dim3(256), 0, s, sa); break;
                 default: hipLaunchKernelGGL((fxk::shared_points_flat_kernel<SD, 2>), dim3(fgrid), dim3(256), 0, s, sa); break;
             }
-            HIP_TRY(hipGetLastError());
+            FX_HIP_TRY(hipGetLastError());
             return FX_OK;
         }
     }
@@ -1483,7 +1422,7 @@ int launch_shared(int order, const fxk::SharedArgs& sa, int ncu, hipStream_t s, 
         bool ok = ns <= 32;
         if (ok) hipLaunchKernelGGL((fxk::shared_points_wave_kernel<SD, 8>), dim3(wgrid), dim3(256), 0, s, sa, nwr);
         if (ok) {
-            HIP_TRY(hipGetLastError());
+            FX_HIP_TRY(hipGetLastError());
             return FX_OK;
         }
     }
@@ -1521,7 +1460,7 @@ int launch_shared(int order, const fxk::SharedArgs& sa, int ncu, hipStream_t s, 
             }
         }
         if (ok) {
-            HIP_TRY(hipGetLastError());
+            FX_HIP_TRY(hipGetLastError());
             return FX_OK;
         }
     }
@@ -1532,7 +1471,7 @@ int launch_shared(int order, const fxk::SharedArgs& sa, int ncu, hipStream_t s, 
         case 1: hipLaunchKernelGGL((fxk::shared_points_kernel<SD, 1>), dim3(rgrid), dim3(256), 0, s, sa); break;
         default: hipLaunchKernelGGL((fxk::shared_points_kernel<SD, 2>), dim3(rgrid), dim3(256), 0, s, sa); break;
     }
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 }  // namespace
@@ -1633,7 +1572,7 @@ int fx_tabulate_batch(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq,
         if (rc != FX_OK) return rc;
         // with per-request cells the order-0 kernels map the points into the element's cell: the tables are derivatives
         // with respect to the ELEMENT's coordinates, and the chain rule follows as a pass over the tables
-        rc = fx_tabulate_batch(ctx, e->high[order], 0, nreq, npts, pts, verts, out, stream);
+        rc = fx_tabulate_batch(ctx, e->high[order].get(), 0, nreq, npts, pts, verts, out, stream);
         if (rc != FX_OK || !verts) return rc;
         return mix_high_order(ctx, e, order, nreq, npts, verts, out, (hipStream_t)stream);
     }
@@ -1696,7 +1635,7 @@ int fx_pushforward_batch(fx_ctx* ctx, const fx_element* e, int mapping, int orde
         hipLaunchKernelGGL(fxk::piola_apply_kernel<2>, dim3(pgrid), dim3(256), 0, (hipStream_t)stream, pa);
     else
         hipLaunchKernelGGL(fxk::piola_apply_kernel<3>, dim3(pgrid), dim3(256), 0, (hipStream_t)stream, pa);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1736,14 +1675,10 @@ int fx_tabulate_batch_shared(fx_ctx* ctx, const fx_element* e, int mapping, int 
     // Reference-cell tables: scratch of THIS call, allocated and released in stream order (hipMallocAsync /
     // hipFreeAsync on the caller's stream), so calls on different streams never share a buffer and the memory
     // returns to the pool only after the streaming kernel below has read it.
-    HIP_TRY(hipSetDevice(ctx->device));
-    double* d_ref = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_ref), need, s));
-    struct Release {
-        double* p;
-        hipStream_t s;
-        ~Release() { (void)hipFreeAsync(p, s); }
-    } release{d_ref, s};
+    FX_HIP_TRY(hipSetDevice(ctx->device));
+    StreamScratch<double> ref;
+    FX_HIP_TRY(ref.alloc(need / sizeof(double), s));
+    double* d_ref = ref.get();
     // the element on its own cell at the shared points, once
     int rc = fx_tabulate_batch(ctx, e, order, 1, npts, ref_pts, nullptr, d_ref, stream);
     if (rc != FX_OK) return rc;
@@ -1787,14 +1722,10 @@ int fx_collapsed_quadrature(fx_ctx* ctx, int sd, int m, const double* verts, dou
     const size_t need = (size_t)2 * 3 * fxk::GJ_MAX * sizeof(double);
     hipStream_t s = (hipStream_t)stream;
     // the 1-D rules: per-call scratch in stream order (see fx_tabulate_batch_shared)
-    HIP_TRY(hipSetDevice(ctx->device));
-    double* d_rules = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_rules), need, s));
-    struct Release {
-        double* p;
-        hipStream_t s;
-        ~Release() { (void)hipFreeAsync(p, s); }
-    } release{d_rules, s};
+    FX_HIP_TRY(hipSetDevice(ctx->device));
+    StreamScratch<double> rules;
+    FX_HIP_TRY(rules.alloc(need / sizeof(double), s));
+    double* d_rules = rules.get();
     ra.rules = d_rules;
     ra.pts = pts;
     ra.wts = wts;
@@ -1805,7 +1736,7 @@ int fx_collapsed_quadrature(fx_ctx* ctx, int sd, int m, const double* verts, dou
     if (sd == 1) hipLaunchKernelGGL(fxk::collapsed_rule_kernel<1>, dim3(grid), dim3(256), 0, s, ra);
     if (sd == 2) hipLaunchKernelGGL(fxk::collapsed_rule_kernel<2>, dim3(grid), dim3(256), 0, s, ra);
     if (sd == 3) hipLaunchKernelGGL(fxk::collapsed_rule_kernel<3>, dim3(grid), dim3(256), 0, s, ra);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1819,7 +1750,7 @@ int fx_classify_tables(fx_ctx* ctx, int64_t ntables, int rows, int npts, double 
     if (!tables || !stats) return fail(FX_EINVAL, "null device pointer");
     fxk::ClassifyArgs ca{tables, stats, rows, npts, rtol};
     hipLaunchKernelGGL(fxk::classify_tables_kernel, dim3((unsigned)ntables), dim3(256), 0, (hipStream_t)stream, ca);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1835,7 +1766,7 @@ int fx_tables_squared_norm(fx_ctx* ctx, int64_t ntables, int rows, int vdim, int
     if (!tables || !weights || !out) return fail(FX_EINVAL, "null device pointer");
     fxk::SquaredNormArgs sa{tables, weights, out, rows, vdim, npts};
     hipLaunchKernelGGL(fxk::squared_norm_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sa, nrows);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1848,7 +1779,7 @@ int fx_tables_point_major(fx_ctx* ctx, int64_t ntables, int rows, int npts, cons
     if (ntables * tiles > 0x7fffffffLL) return fail(FX_EINVAL, "too many tiles for one launch");
     fxk::PointMajorArgs pa{in, out, rows, npts};
     hipLaunchKernelGGL(fxk::point_major_kernel, dim3((unsigned)(ntables * tiles)), dim3(256), 0, (hipStream_t)stream, pa);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1899,8 +1830,9 @@ int check_work_queues(fx_ctx* ctx) {
     constexpr int N = fx::CounterHandout::BLOCK;
     unsigned int flags[N * 32];
     bool bad = false;
-    for (unsigned long long* block : ctx->queue_blocks) {
-        HIP_TRY(hipMemcpy(flags, block, sizeof flags, hipMemcpyDeviceToHost));
+    for (const auto& owned : ctx->queue_blocks) {
+        unsigned long long* block = owned.get();
+        FX_HIP_TRY(hipMemcpy(flags, block, sizeof flags, hipMemcpyDeviceToHost));
         for (int i = 0; i < N; ++i)
             if (flags[i * 32 + 2]) {
                 (void)hipMemset(block, 0, N * 128);
@@ -1921,17 +1853,17 @@ int fx_time_tabulate_batch(fx_ctx* ctx, const fx_element* e, int order, int64_t 
     if (rc != FX_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t t0, t1;
-    HIP_TRY(hipEventCreate(&t0));
-    HIP_TRY(hipEventCreate(&t1));
-    HIP_TRY(hipEventRecord(t0, s));
+    FX_HIP_TRY(hipEventCreate(&t0));
+    FX_HIP_TRY(hipEventCreate(&t1));
+    FX_HIP_TRY(hipEventRecord(t0, s));
     for (int i = 0; i < reps; ++i) {
         rc = run_tabulate(ctx, e, order, L, s);
         if (rc != FX_OK) break;
     }
-    HIP_TRY(hipEventRecord(t1, s));
-    HIP_TRY(hipEventSynchronize(t1));
+    FX_HIP_TRY(hipEventRecord(t1, s));
+    FX_HIP_TRY(hipEventSynchronize(t1));
     float total = 0.f;
-    HIP_TRY(hipEventElapsedTime(&total, t0, t1));
+    FX_HIP_TRY(hipEventElapsedTime(&total, t0, t1));
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);
     *ms = total / reps;
@@ -1943,32 +1875,25 @@ int fx_tabulate_batch_host(fx_ctx* ctx, const fx_element* e, int order, int64_t 
                            const double* verts, double* out) {
     if (!ctx || !e) return fail(FX_EINVAL, "null context/element");
     if (order < 0 || order > 2) return fail(order < 0 ? FX_EINVAL : FX_ENOTIMPL, "unsupported derivative order %d", order);
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     const int ntab = fx::binom(e->sd + order, e->sd);
     size_t pbytes = (size_t)nreq * npts * e->sd * 8, vbytes = (size_t)nreq * (e->sd + 1) * e->sd * 8;
     size_t obytes = (size_t)nreq * ntab * e->ndof * e->vdim * npts * 8;
     if (pbytes == 0 || obytes == 0) return FX_OK;
-    double *dp = nullptr, *dv = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(&dp, pbytes));
-    HIP_TRY(hipMalloc(&dout, obytes));
-    HIP_TRY(hipMemcpy(dp, pts, pbytes, hipMemcpyHostToDevice));
-    if (verts) {
-        HIP_TRY(hipMalloc(&dv, vbytes));
-        HIP_TRY(hipMemcpy(dv, verts, vbytes, hipMemcpyHostToDevice));
-    }
-    int rc = fx_tabulate_batch(ctx, e, order, nreq, npts, dp, dv, dout, nullptr);
+    DeviceBuffer<double> dp, dv, dout;
+    FX_HIP_TRY(dp.upload(pts, pbytes / 8));
+    FX_HIP_TRY(dout.alloc(obytes / 8));
+    if (verts) FX_HIP_TRY(dv.upload(verts, vbytes / 8));
+    int rc = fx_tabulate_batch(ctx, e, order, nreq, npts, dp.get(), dv.get(), dout.get(), nullptr);
     if (rc == FX_OK) {
         hipError_t he = hipDeviceSynchronize();
         if (he != hipSuccess) rc = fail(FX_EHIP, "tabulate kernel: %s", hipGetErrorString(he));
     }
     if (rc == FX_OK) rc = check_work_queues(ctx);
     if (rc == FX_OK) {
-        hipError_t he = hipMemcpy(out, dout, obytes, hipMemcpyDeviceToHost);
+        hipError_t he = hipMemcpy(out, dout.get(), obytes, hipMemcpyDeviceToHost);
         if (he != hipSuccess) rc = fail(FX_EHIP, "copy back: %s", hipGetErrorString(he));
     }
-    (void)hipFree(dp);
-    (void)hipFree(dout);
-    if (dv) (void)hipFree(dv);
     return rc;
 }
 
@@ -1981,7 +1906,7 @@ int fx_riesz_assemble(fx_ctx* ctx, int nrows, int nq, int nexp, const double* wt
     int grid = (int)((total + 255) / 256);
     hipLaunchKernelGGL(fxk::riesz_assemble_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, nrows, nq, nexp, wts,
                        ev, mat);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -1993,22 +1918,21 @@ int fx_vandermonde_solve_batch(fx_ctx* ctx, int64_t nsys, int ndof, int m, const
     if (lds > 150 * 1024) {
         // beyond the LDS: the same elimination with M and the right-hand sides in a global workspace
         if (nsys > 65535) return fail(FX_EINVAL, "fx_vandermonde_solve_batch: too many large systems in one call");
-        double* ws = nullptr;
-        HIP_TRY(hipMalloc(&ws, (size_t)nsys * lds));
+        DeviceBuffer<double> ws;  // (released after the synchronisation below)
+        FX_HIP_TRY(ws.alloc((size_t)nsys * lds / 8));
         hipLaunchKernelGGL(fxk::vandermonde_solve_kernel<true>, dim3((unsigned)nsys), dim3(256), 0, (hipStream_t)stream, ndof, m,
-                           A, B, X, Vout, info, ws);
+                           A, B, X, Vout, info, ws.get());
         hipError_t he = hipGetLastError();
         if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
-        (void)hipFree(ws);
         if (he != hipSuccess) return fail(FX_EHIP, "fx_vandermonde_solve_batch: %s", hipGetErrorString(he));
         return FX_OK;
     }
     auto kern = fxk::vandermonde_solve_kernel<false>;
     if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)nsys), dim3(256), lds, (hipStream_t)stream, ndof, m, A, B, X, Vout, info,
                        (double*)nullptr);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2017,8 +1941,8 @@ int fx_line_element_create(fx_ctx* ctx, int nn, const double* nodes, fx_line_ele
     if (!ctx || !nodes || !out) return fail(FX_EINVAL, "fx_line_element_create: null argument");
     // (up to NN_MAX nodes: register-resident kernels, tensor products, prisms; beyond: fx_line_tabulate_batch only)
     if (nn < 1 || nn > fxk::NN_BIG_MAX) return fail(FX_ENOTIMPL, "1-D Lagrange with %d nodes (max %d)", nn, fxk::NN_BIG_MAX);
-    HIP_TRY(hipSetDevice(ctx->device));
-    fx_line_element* e = new fx_line_element;
+    FX_HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<fx_line_element> e(new fx_line_element);
     e->ctx = ctx;
     e->nn = nn;
     e->nodes.assign(nodes, nodes + nn);
@@ -2029,10 +1953,7 @@ int fx_line_element_create(fx_ctx* ctx, int nn, const double* nodes, fx_line_ele
     for (int j = 0; j < nn; ++j) {
         double p = 1.0;
         for (int i = 0; i < nn; ++i) p *= D[(size_t)i * nn + j];
-        if (p == 0.0) {
-            delete e;
-            return fail(FX_EINVAL, "repeated interpolation node");
-        }
+        if (p == 0.0) return fail(FX_EINVAL, "repeated interpolation node");
         w[j] = 1.0 / p;
     }
     for (int i = 0; i < nn; ++i)
@@ -2047,28 +1968,22 @@ int fx_line_element_create(fx_ctx* ctx, int nn, const double* nodes, fx_line_ele
     buf.insert(buf.end(), e->nodes.begin(), e->nodes.end());
     buf.insert(buf.end(), w.begin(), w.end());
     buf.insert(buf.end(), D.begin(), D.end());
-    hipError_t he = hipMalloc(&e->d_buf, buf.size() * 8);
-    if (he == hipSuccess) he = hipMemcpy(e->d_buf, buf.data(), buf.size() * 8, hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        fx_line_element_destroy(e);
-        return fail(FX_EHIP, "fx_line_element_create: %s", hipGetErrorString(he));
-    }
-    *out = e;
+    const hipError_t he = e->d_buf.upload(buf.data(), buf.size());
+    if (he != hipSuccess) return fail(FX_EHIP, "fx_line_element_create: %s", hipGetErrorString(he));
+    *out = e.release();
     return FX_OK;
 }
 
 int fx_line_element_destroy(fx_line_element* e) {
-    if (!e) return FX_OK;
-    if (e->d_buf) (void)hipFree(e->d_buf);
     delete e;
     return FX_OK;
 }
 
 static fxk::LineDesc line_desc(const fx_line_element* e) {
     fxk::LineDesc L;
-    L.nodes = e->d_buf;
-    L.wts = e->d_buf + e->nn;
-    L.dmat = e->d_buf + 2 * e->nn;
+    L.nodes = e->d_buf.get();
+    L.wts = e->d_buf.get() + e->nn;
+    L.dmat = e->d_buf.get() + 2 * e->nn;
     L.nn = e->nn;
     return L;
 }
@@ -2090,7 +2005,7 @@ int fx_line_tabulate_batch(fx_ctx* ctx, const fx_line_element* e, int order, int
     else
         hipLaunchKernelGGL(fxk::line_tabulate_kernel, dim3(grid), dim3(128), 0, (hipStream_t)stream, line_desc(e), order,
                            (long long)nreq, npts, pts, out);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2152,7 +2067,7 @@ static int tensor_launch(fx_ctx* ctx, int nf, const fx_line_element* const* fact
     a.pts = pts;
     a.out = out;
     if (try_tensor_small(ctx, grid_mode, a, (hipStream_t)stream)) {
-        HIP_TRY(hipGetLastError());
+        FX_HIP_TRY(hipGetLastError());
         return FX_OK;
     }
     if (lds > 150 * 1024) return fail(FX_ENOTIMPL, "factor tables exceed LDS (%zu bytes)", lds);
@@ -2173,9 +2088,9 @@ static int tensor_launch(fx_ctx* ctx, int nf, const fx_line_element* const* fact
         case 5: kern = grid_mode ? (TensorKern)fxk::tensor_tabulate_kernel<true, 5> : (TensorKern)fxk::tensor_tabulate_kernel<false, 5>; break;
     }
     if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2211,7 +2126,7 @@ int fx_prism_tabulate_batch(fx_ctx* ctx, const fx_element* tri, const fx_line_el
     memset(&a, 0, sizeof a);
     a.pts = pts;
     a.out = out;
-    a.cmat = tri->d_cmat;
+    a.cmat = tri->d_cmat.get();
     for (size_t k = 0; k < tri->prog.steps.size(); ++k) {
         a.coef[3 * k + 0] = tri->prog.steps[k].A;
         a.coef[3 * k + 1] = tri->prog.steps[k].B;
@@ -2239,7 +2154,7 @@ int fx_prism_tabulate_batch(fx_ctx* ctx, const fx_element* tri, const fx_line_el
     if (tri->n == 2) ok = launch_prism_small_nn<2>(line->nn, order, a, grid, lds, (hipStream_t)stream);
     if (tri->n == 3) ok = launch_prism_small_nn<3>(line->nn, order, a, grid, lds, (hipStream_t)stream);
     if (!ok) return fail(FX_ENOTIMPL, "fx_prism_tabulate_batch: no instance for degree %d x %d nodes, order %d", tri->n, line->nn, order);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2310,45 +2225,25 @@ int project_derivative_matrices(fx_ctx* ctx, fx_element* e, int order, std::vect
     const int m = e->n + 1;
     int nq = 1;
     for (int d = 0; d < sd; ++d) nq *= m;
-    double *d_pts = nullptr, *d_wts = nullptr, *d_tab = nullptr;
-    fx_element* raw = new fx_element;
-    raw->ctx = ctx;
-    raw->sd = sd;
-    raw->n = e->n;
-    raw->variant = e->variant;
-    raw->nexp = nexp;
-    raw->scale = e->scale;
-    memcpy(raw->A0, e->A0, sizeof raw->A0);
-    memcpy(raw->b0, e->b0, sizeof raw->b0);
-    raw->prog = e->prog;
-    raw->raw_expansion = true;  // (no C0 transform: the projection is onto the raw recurrence basis)
     std::vector<double> tab((size_t)ntab * nexp * nq), wts(nq);
-    auto cleanup = [&]() {
-        if (d_pts) (void)hipFree(d_pts);
-        if (d_wts) (void)hipFree(d_wts);
-        if (d_tab) (void)hipFree(d_tab);
-        fx_element_destroy(raw);
-    };
-    int rc = FX_OK;
-    hipError_t he = hipMalloc(&raw->d_steps, std::max<size_t>(1, raw->prog.steps.size()) * sizeof(fxk::Step));
-    if (he == hipSuccess && !raw->prog.steps.empty())
-        he = hipMemcpy(raw->d_steps, raw->prog.steps.data(), raw->prog.steps.size() * sizeof(fxk::Step), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc(&d_pts, (size_t)nq * sd * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc(&d_wts, (size_t)nq * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc(&d_tab, tab.size() * sizeof(double));
-    if (he != hipSuccess) {
-        cleanup();
-        return fail(FX_EHIP, "stacked matrix: %s", hipGetErrorString(he));
-    }
-    rc = upload_coeffs(raw, nexp, 1, nullptr);
-    if (rc == FX_OK) rc = fx_collapsed_quadrature(ctx, sd, m, verts, d_pts, d_wts, nullptr);
-    if (rc == FX_OK) rc = fx_tabulate_batch(ctx, raw, order, 1, nq, d_pts, nullptr, d_tab, nullptr);
+    // the raw recurrence basis on the element's cell (no C0 transform: the projection is onto the raw basis) and the scratch
+    // of the projection: locals, released on every way out
+    std::unique_ptr<fx_element> raw;
+    DeviceBuffer<double> d_pts, d_wts, d_tab;
+    hipError_t he = make_element_shell(ctx, sd, e->n, e->variant, e->scale, e->A0, e->b0, e->prog, raw);
+    if (he == hipSuccess) he = d_pts.alloc((size_t)nq * sd);
+    if (he == hipSuccess) he = d_wts.alloc((size_t)nq);
+    if (he == hipSuccess) he = d_tab.alloc(tab.size());
+    if (he != hipSuccess) return fail(FX_EHIP, "stacked matrix: %s", hipGetErrorString(he));
+    raw->raw_expansion = true;
+    int rc = upload_coeffs(raw.get(), nexp, 1, nullptr);
+    if (rc == FX_OK) rc = fx_collapsed_quadrature(ctx, sd, m, verts, d_pts.get(), d_wts.get(), nullptr);
+    if (rc == FX_OK) rc = fx_tabulate_batch(ctx, raw.get(), order, 1, nq, d_pts.get(), nullptr, d_tab.get(), nullptr);
     if (rc == FX_OK) {
-        he = hipMemcpy(tab.data(), d_tab, tab.size() * sizeof(double), hipMemcpyDeviceToHost);
-        if (he == hipSuccess) he = hipMemcpy(wts.data(), d_wts, wts.size() * sizeof(double), hipMemcpyDeviceToHost);
+        he = hipMemcpy(tab.data(), d_tab.get(), tab.size() * sizeof(double), hipMemcpyDeviceToHost);
+        if (he == hipSuccess) he = hipMemcpy(wts.data(), d_wts.get(), wts.size() * sizeof(double), hipMemcpyDeviceToHost);
         if (he != hipSuccess) rc = fail(FX_EHIP, "stacked matrix: %s", hipGetErrorString(he));
     }
-    cleanup();
     if (rc != FX_OK) return rc;
     // M (symmetric) and the right-hand sides R_alpha^T, side by side
     const int nrhs = (ntab - 1) * nexp;
@@ -2422,7 +2317,7 @@ int mix_any_order(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, int
     if (sd == 1) hipLaunchKernelGGL((fxk::table_mix_any_kernel<1>), grid, dim3(256), lds, s, ma);
     else if (sd == 2) hipLaunchKernelGGL((fxk::table_mix_any_kernel<2>), grid, dim3(256), lds, s, ma);
     else hipLaunchKernelGGL((fxk::table_mix_any_kernel<3>), grid, dim3(256), lds, s, ma);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2469,7 +2364,7 @@ int mix_high_order(fx_ctx* ctx, const fx_element* e, int order, int64_t nreq, in
     else if (sd == 2) hipLaunchKernelGGL((fxk::table_mix_high_kernel<2, 4>), grid, dim3(256), 0, s, ma);
     else if (order == 3) hipLaunchKernelGGL((fxk::table_mix_high_kernel<3, 3>), grid, dim3(256), 0, s, ma);
     else hipLaunchKernelGGL((fxk::table_mix_high_kernel<3, 4>), grid, dim3(256), 0, s, ma);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2553,29 +2448,12 @@ int ensure_high_order(fx_ctx* ctx, fx_element* e, int order) {
         }
     }
     // the internal element: same cell, same recurrence, no C0 transform (hC already carries it), rows = all tables
-    fx_element* h = new fx_element;
-    h->ctx = ctx;
-    h->sd = sd;
-    h->n = e->n;
-    h->variant = e->variant;
-    h->nexp = nexp;
-    h->scale = e->scale;
-    memcpy(h->A0, e->A0, sizeof h->A0);
-    memcpy(h->b0, e->b0, sizeof h->b0);
-    h->prog = e->prog;
-    hipError_t he = hipMalloc(&h->d_steps, std::max<size_t>(1, h->prog.steps.size()) * sizeof(fxk::Step));
-    if (he == hipSuccess && !h->prog.steps.empty())
-        he = hipMemcpy(h->d_steps, h->prog.steps.data(), h->prog.steps.size() * sizeof(fxk::Step), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        fx_element_destroy(h);
-        return fail(FX_EHIP, "derivative order %d: %s", order, hipGetErrorString(he));
-    }
-    int rc = upload_coeffs(h, ntab * rows, 1, S.data());
-    if (rc != FX_OK) {
-        fx_element_destroy(h);
-        return rc;
-    }
-    e->high[order] = h;
+    std::unique_ptr<fx_element> h;
+    const hipError_t he = make_element_shell(ctx, sd, e->n, e->variant, e->scale, e->A0, e->b0, e->prog, h);
+    if (he != hipSuccess) return fail(FX_EHIP, "derivative order %d: %s", order, hipGetErrorString(he));
+    const int rc = upload_coeffs(h.get(), ntab * rows, 1, S.data());
+    if (rc != FX_OK) return rc;
+    e->high[order] = std::move(h);
     e->high_state[order] = 1;
     return FX_OK;
 }
@@ -2628,13 +2506,10 @@ int ensure_stacked(fx_ctx* ctx, fx_element* e, int order) {
                 const int mem = member[4 * ks + (lane >> 4)];
                 if (row < R && mem >= 0) F[((size_t)rt * KS + ks) * 64 + lane] = S[(size_t)row * nexp + mem];
             }
-    double* d_f = nullptr;
-    HIP_TRY(hipMalloc(&d_f, F.size() * sizeof(double)));
-    if (hipMemcpy(d_f, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d_f);
-        (void)hipGetLastError();  // (the failed call left HIP's sticky error set: the next launch check must not report it)
-        return fail(FX_EHIP, "ensure_stacked: copy of the stacked matrix failed");
-    }
+    // the up to three layouts as locals, moved into the element together at the end (build-then-commit, device_buffer.hpp)
+    DeviceBuffer<double> d_f, d_fd, d_fp;
+    if (d_f.upload(F.data(), F.size()) != hipSuccess)
+        return fail(FX_EHIP, "ensure_stacked: allocation or copy of the stacked matrix failed");
     if (order >= 1) {  // dof-major tiles for the instances that apply the chain rule across the tables themselves (per-request cells)
         const int RTd = (rows + 15) / 16;
         std::vector<double> Fd((size_t)(RTd * ntab + 1) * KS * 64, 0.0);
@@ -2647,15 +2522,8 @@ int ensure_stacked(fx_ctx* ctx, fx_element* e, int order) {
                         if (r < rows && mem >= 0)
                             Fd[(((size_t)i * ntab + t) * KS + ks) * 64 + lane] = S[((size_t)t * rows + r) * nexp + mem];
                     }
-        double* d_fd = nullptr;
-        if (hipMalloc(&d_fd, Fd.size() * sizeof(double)) != hipSuccess ||
-            hipMemcpy(d_fd, Fd.data(), Fd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            if (d_fd) (void)hipFree(d_fd);
-            (void)hipFree(d_f);
-            (void)hipGetLastError();  // (the failed call left HIP's sticky error set: the next launch check must not report it)
+        if (d_fd.upload(Fd.data(), Fd.size()) != hipSuccess)
             return fail(FX_EHIP, "ensure_stacked: allocation or copy of the dof-major stacked matrix failed");
-        }
-        e->d_astack_dm[order] = d_fd;
     }
     if (e->vdim == sd && sd >= 2) {  // vector-valued: dof-major tiles with the components of a dof in one lane (fused Piola map)
         const int TR = fxk::stacked_tile_rows(sd, 1);
@@ -2671,19 +2539,12 @@ int ensure_stacked(fx_ctx* ctx, fx_element* e, int order) {
                         if (tr >= 0 && TR * i + tr < rows && mem >= 0)
                             Fp[(((size_t)i * ntab + t) * KS + ks) * 64 + lane] = S[((size_t)t * rows + TR * i + tr) * nexp + mem];
                     }
-        double* d_fp = nullptr;
-        if (hipMalloc(&d_fp, Fp.size() * sizeof(double)) != hipSuccess ||
-            hipMemcpy(d_fp, Fp.data(), Fp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            if (d_fp) (void)hipFree(d_fp);
-            if (e->d_astack_dm[order]) (void)hipFree(e->d_astack_dm[order]);
-            e->d_astack_dm[order] = nullptr;
-            (void)hipFree(d_f);
-            (void)hipGetLastError();  // (the failed call left HIP's sticky error set: the next launch check must not report it)
+        if (d_fp.upload(Fp.data(), Fp.size()) != hipSuccess)
             return fail(FX_EHIP, "ensure_stacked: allocation or copy of the component-major stacked matrix failed");
-        }
-        e->d_astack_dmp[order] = d_fp;
     }
-    e->d_astack[order] = d_f;
+    e->d_astack[order] = std::move(d_f);
+    e->d_astack_dm[order] = std::move(d_fd);
+    e->d_astack_dmp[order] = std::move(d_fp);
     e->stack_state[order] = 1;
     return FX_OK;
 }
@@ -2703,10 +2564,10 @@ struct fx_macro_element {
     std::vector<int> map;        // [ncell][nexp]
     std::vector<double> cscale;  // [ncell]
     int KS = 0, MT = 0;
-    fxk::Step* d_steps = nullptr;
-    double* d_cells = nullptr;
-    double* d_afrag = nullptr;
-    double* d_cmat = nullptr;  // [ncell][rows][nexp] blocks of the lane-local kernel (macro_small.hpp)
+    DeviceBuffer<fxk::Step> d_steps;
+    DeviceBuffer<double> d_cells;
+    DeviceBuffer<double> d_afrag;
+    DeviceBuffer<double> d_cmat;  // [ncell][rows][nexp] blocks of the lane-local kernel (macro_small.hpp)
 };
 
 namespace {
@@ -2757,22 +2618,15 @@ int macro_upload_coeffs(fx_macro_element* e, int ndof, int vdim, const double* c
                 }
             }
     std::vector<double> F = fx::pack_a_fragments(S, rows, K);
-    if (e->d_afrag) {
-        (void)hipFree(e->d_afrag);
-        e->d_afrag = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_afrag, F.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_afrag, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice));
+    DeviceBuffer<double> d_afrag, d_cmat;  // build-then-commit, as upload_coeffs
+    FX_HIP_TRY(d_afrag.upload(F.data(), F.size()));
     std::vector<double> CM((size_t)e->ncell * rows * nexp);
     for (int c = 0; c < e->ncell; ++c)
         for (int i = 0; i < rows; ++i)
             for (int k = 0; k < nexp; ++k) CM[((size_t)c * rows + i) * nexp + k] = S[(size_t)i * K + (size_t)c * nexp + k];
-    if (e->d_cmat) {
-        (void)hipFree(e->d_cmat);
-        e->d_cmat = nullptr;
-    }
-    HIP_TRY(hipMalloc(&e->d_cmat, CM.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(e->d_cmat, CM.data(), CM.size() * sizeof(double), hipMemcpyHostToDevice));
+    FX_HIP_TRY(d_cmat.upload(CM.data(), CM.size()));
+    e->d_afrag = std::move(d_afrag);
+    e->d_cmat = std::move(d_cmat);
     e->ndof = ndof;
     e->vdim = vdim;
     e->MT = (rows + 15) / 16;
@@ -2784,9 +2638,9 @@ template <int SD, int ORDER>
 int launch_macro_one(const fxk::TabArgs& a, int grid, int lds_bytes, hipStream_t s) {
     auto kern = fxk::tabulate_simplex_kernel<SD, ORDER, 1, 0, 0, true>;
     if (lds_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds_bytes, s, a);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2812,9 +2666,9 @@ template <int SD, int N, int ORDER>
 int launch_macro_small_one(const fxk::MacroSmallArgs& a, int grid, int lds_bytes, hipStream_t s) {
     auto kern = fxk::tabulate_macro_small<SD, N, ORDER, MACRO_SMALL_NW>;
     if (lds_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * MACRO_SMALL_NW), lds_bytes, s, a);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -2840,11 +2694,6 @@ constexpr MacroSmallShape kMacroSmallShapes[] = {macro_small_row<2, 1, 2>(), mac
 extern "C" {
 
 int fx_macro_element_destroy(fx_macro_element* e) {
-    if (!e) return FX_OK;
-    if (e->d_steps) (void)hipFree(e->d_steps);
-    if (e->d_cells) (void)hipFree(e->d_cells);
-    if (e->d_afrag) (void)hipFree(e->d_afrag);
-    if (e->d_cmat) (void)hipFree(e->d_cmat);
     delete e;
     return FX_OK;
 }
@@ -2860,8 +2709,8 @@ int fx_macro_element_create(fx_ctx* ctx, int sd, int n, int variant, double scal
     if (ncell < 1 || ncell > 32) return fail(FX_EINVAL, "a macro cell needs 1..32 sub-cells, got %d", ncell);
     if (ndof < 1 || vdim < 1 || nmacro < 1) return fail(FX_EINVAL, "bad ndof/vdim/nmacro");
     if (!(scale > 0.0)) return fail(FX_EINVAL, "a macro expansion set needs an explicit positive scale");
-    HIP_TRY(hipSetDevice(ctx->device));
-    fx_macro_element* e = new fx_macro_element;
+    FX_HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<fx_macro_element> e(new fx_macro_element);
     e->ctx = ctx;
     e->sd = sd;
     e->n = n;
@@ -2871,26 +2720,17 @@ int fx_macro_element_create(fx_ctx* ctx, int sd, int n, int variant, double scal
     e->nmacro = nmacro;
     e->map.assign(cell_node_map, cell_node_map + (size_t)ncell * e->nexp);
     for (int m : e->map)
-        if (m < 0 || m >= nmacro) {
-            delete e;
-            return fail(FX_EINVAL, "cell_node_map entry %d outside [0, %d)", m, nmacro);
-        }
+        if (m < 0 || m >= nmacro) return fail(FX_EINVAL, "cell_node_map entry %d outside [0, %d)", m, nmacro);
     e->cscale.assign(ncell, 1.0);
     if (cell_scale) e->cscale.assign(cell_scale, cell_scale + ncell);
-    if (!host_cell_map(sd, parent_verts ? parent_verts : UFC[sd - 1], e->A0, e->b0)) {
-        delete e;
-        return fail(FX_EINVAL, "degenerate cell");
-    }
+    if (!host_cell_map(sd, parent_verts ? parent_verts : UFC[sd - 1], e->A0, e->b0)) return fail(FX_EINVAL, "degenerate cell");
     double A0inv[9];
     invert_small(sd, e->A0, A0inv);
     std::vector<double> cells(16 + (size_t)ncell * 28, 0.0);
     barycentric_rows(sd, e->A0, e->b0, A0inv, e->b0, &cells[0], &cells[12]);
     for (int c = 0; c < ncell; ++c) {
         double Ac[9], bc[3];
-        if (!host_cell_map(sd, cell_verts + (size_t)c * (sd + 1) * sd, Ac, bc)) {
-            delete e;
-            return fail(FX_EINVAL, "degenerate sub-cell %d", c);
-        }
+        if (!host_cell_map(sd, cell_verts + (size_t)c * (sd + 1) * sd, Ac, bc)) return fail(FX_EINVAL, "degenerate sub-cell %d", c);
         double* cd = &cells[16 + (size_t)c * 28];
         for (int i = 0; i < sd; ++i) {  // X_c = Ac A0inv (xi - b0) + bc
             double shift = 0.0;
@@ -2906,28 +2746,18 @@ int fx_macro_element_create(fx_ctx* ctx, int sd, int n, int variant, double scal
     }
     e->prog = fx::build_program(sd, n, variant, scale);
     if (variant == FX_VARIANT_BUBBLE) e->T = fx::c0_transform(sd, n);
-    size_t sbytes = std::max<size_t>(1, e->prog.steps.size()) * sizeof(fxk::Step);
-    hipError_t he = hipMalloc(&e->d_steps, sbytes);
-    if (he == hipSuccess && !e->prog.steps.empty())
-        he = hipMemcpy(e->d_steps, e->prog.steps.data(), e->prog.steps.size() * sizeof(fxk::Step), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMalloc(&e->d_cells, cells.size() * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpy(e->d_cells, cells.data(), cells.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
-        fx_macro_element_destroy(e);
-        return fail(FX_EHIP, "fx_macro_element_create: %s", hipGetErrorString(he));
-    }
-    int rc = macro_upload_coeffs(e, ndof, vdim, coeffs);
-    if (rc != FX_OK) {
-        fx_macro_element_destroy(e);
-        return rc;
-    }
-    *out = e;
+    hipError_t he = e->d_steps.upload(reinterpret_cast<const fxk::Step*>(e->prog.steps.data()), e->prog.steps.size(), 1);
+    if (he == hipSuccess) he = e->d_cells.upload(cells.data(), cells.size());
+    if (he != hipSuccess) return fail(FX_EHIP, "fx_macro_element_create: %s", hipGetErrorString(he));
+    const int rc = macro_upload_coeffs(e.get(), ndof, vdim, coeffs);
+    if (rc != FX_OK) return rc;
+    *out = e.release();
     return FX_OK;
 }
 
 int fx_macro_element_set_coeffs(fx_macro_element* e, int ndof, int vdim, const double* coeffs) {
     if (!e || ndof < 1 || vdim < 1) return fail(FX_EINVAL, "fx_macro_element_set_coeffs: bad argument");
-    HIP_TRY(hipSetDevice(e->ctx->device));
+    FX_HIP_TRY(hipSetDevice(e->ctx->device));
     return macro_upload_coeffs(e, ndof, vdim, coeffs);
 }
 
@@ -2941,7 +2771,7 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
     if (!pts || !out) return fail(FX_EINVAL, "null device pointer");
     const int ntab = fx::binom(e->sd + order, e->sd);
     const int rows = e->ndof * e->vdim;
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     {   // lane-local kernel for the registered low-order shapes
         const bool nosmall = (ctx->policy & FX_POLICY_NO_MACRO_SMALL) != 0;
         const long long cmat_doubles = ((long long)e->ncell * rows * e->nexp + 1) & ~1LL;
@@ -2969,8 +2799,8 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
             sa.pts = pts;
             sa.verts = verts;
             sa.out = out;
-            sa.cmat = e->d_cmat;
-            sa.cells = e->d_cells;
+            sa.cmat = e->d_cmat.get();
+            sa.cells = e->d_cells.get();
             for (size_t k = 0; k < e->prog.steps.size(); ++k) {
                 sa.coef[3 * k + 0] = e->prog.steps[k].A;
                 sa.coef[3 * k + 1] = e->prog.steps[k].B;
@@ -3003,8 +2833,8 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
     a.pts = pts;
     a.verts = verts;
     a.out = out;
-    a.afrag = e->d_afrag;
-    a.steps = e->d_steps;
+    a.afrag = e->d_afrag.get();
+    a.steps = e->d_steps.get();
     a.phi0 = e->prog.phi0;
     memcpy(a.A0, e->A0, sizeof a.A0);
     memcpy(a.b0, e->b0, sizeof a.b0);
@@ -3016,7 +2846,7 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
     a.KS = e->KS;
     a.MT = e->MT;
     a.ntab = ntab;
-    a.cells = e->d_cells;
+    a.cells = e->d_cells.get();
     a.ncell = e->ncell;
     a.unique = (e->variant == FX_VARIANT_BUBBLE && order == 0) ? 1 : 0;
     // work-item shape under a per-wave LDS budget (as for the generic kernel, with the K rows of all sub-cells)
@@ -3047,7 +2877,7 @@ int fx_macro_tabulate_batch(fx_ctx* ctx, const fx_macro_element* e, int order, i
     const int lds_bytes = (a.phi_doubles + a.stage_doubles) * 8;
     const int per_cu = std::max(1, std::min(16, ctx->lds_per_cu / std::max(1, lds_bytes)));
     const int grid = (int)std::max<long long>(1, std::min<long long>(a.nitems, (long long)ctx->num_cu * per_cu * 4));
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     switch (e->sd) {
         case 1: return launch_macro_sd<1>(order, a, grid, lds_bytes, (hipStream_t)stream);
         case 2: return launch_macro_sd<2>(order, a, grid, lds_bytes, (hipStream_t)stream);
@@ -3084,7 +2914,7 @@ int fx_comm_create(fx_ctx* ctx, int nranks, int rank, const unsigned char* id, f
     if (!ctx || !id || !out) return fail(FX_EINVAL, "fx_comm_create: null argument");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(FX_EINVAL, "fx_comm_create: rank %d of %d", rank, nranks);
     if (fx_comm_available() != FX_OK) return FX_EHIP;
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
     ncclComm_t c = nullptr;
@@ -3131,7 +2961,7 @@ int fx_allgather_tables(fx_comm* c, const double* send, double* recv, int64_t co
     if (!send || !recv) return fail(FX_EINVAL, "fx_allgather_tables: null device pointer");
     const fxcomm::Api& a = fxcomm::api();
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(c->ctx->device));
+    FX_HIP_TRY(hipSetDevice(c->ctx->device));
     c->remember(s);
     if (algo == FX_GATHER_RING) {
         if (stride != count || offset != 0)
@@ -3141,7 +2971,7 @@ int fx_allgather_tables(fx_comm* c, const double* send, double* recv, int64_t co
     }
     if (algo != FX_GATHER_DIRECT) return fail(FX_EINVAL, "fx_allgather_tables: unknown algorithm %d", algo);
     double* mine = recv + (size_t)c->rank * stride + offset;
-    if (mine != send) HIP_TRY(hipMemcpyAsync(mine, send, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (mine != send) FX_HIP_TRY(hipMemcpyAsync(mine, send, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (c->nranks == 1) return FX_OK;
     NCCL_TRY(a.GroupStart());
     ncclResult_t bad = ncclSuccess;
@@ -3203,7 +3033,7 @@ int fx_table_outer_batch(fx_ctx* ctx, int order, int sdA, int sdB, int64_t nreq,
         a.tA[t] = (unsigned char)(std::find(TA.begin(), TA.end(), aa) - TA.begin());
         a.tB[t] = (unsigned char)(std::find(TB.begin(), TB.end(), bb) - TB.begin());
     }
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     // factor tables of a group of requests staged in LDS when they fit a 16 KB tile (and the group's output < 2^24 entries)
     const long long sizeA = (long long)a.ntabA * rowsA * vdimA * npts, sizeB = (long long)a.ntabB * rowsB * vdimB * npts;
     const long long nrows = (long long)a.ntab * rowsA * rowsB * vdim, S = nrows * npts;
@@ -3220,15 +3050,15 @@ int fx_table_outer_batch(fx_ctx* ctx, int order, int sdA, int sdB, int64_t nreq,
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)ctx->lds_per_cu / lds));
         const int grid = (int)std::max<long long>(1, std::min<long long>(ngroups, (long long)ctx->num_cu * per_cu));
         if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fxk::table_outer_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            FX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fxk::table_outer_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(fxk::table_outer_lds_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, la);
-        HIP_TRY(hipGetLastError());
+        FX_HIP_TRY(hipGetLastError());
         return FX_OK;
     }
     const long long units = nreq * a.ntab;
     const int grid = (int)std::max<long long>(1, std::min<long long>(units, (long long)ctx->num_cu * 16));
     hipLaunchKernelGGL(fxk::table_outer_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -3248,10 +3078,10 @@ int fx_map_points(fx_ctx* ctx, int din, int dout, const double* M, const double*
     a.dout = dout;
     for (int i = 0; i < dout * din; ++i) a.M[i] = M[i];
     for (int i = 0; i < dout; ++i) a.b[i] = b[i];
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     const int grid = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)ctx->num_cu * 16));
     hipLaunchKernelGGL(fxk::map_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -3285,11 +3115,11 @@ int fx_jacobi_batch(fx_ctx* ctx, double a, double b, int n, int order, int64_t n
         for (int l = 0; l < order; ++l) z *= 0.5 * (f + l);
         A.z[j] = z;
     }
-    HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
     const long long want = (npts + 255) / 256;
     const int grid = (int)std::max<long long>(1, std::min<long long>(want, (long long)ctx->num_cu * 16));
     hipLaunchKernelGGL(fxk::jacobi_batch_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, A);
-    HIP_TRY(hipGetLastError());
+    FX_HIP_TRY(hipGetLastError());
     return FX_OK;
 }
 
@@ -3297,8 +3127,8 @@ int fx_jacobi_batch(fx_ctx* ctx, double a, double b, int n, int order, int64_t n
 // id (work_queue.hpp)?  Synchronises `stream` first.
 int fx_ctx_check(fx_ctx* ctx, void* stream) {
     if (!ctx) return fail(FX_EINVAL, "fx_ctx_check: null context");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    FX_HIP_TRY(hipSetDevice(ctx->device));
+    FX_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return check_work_queues(ctx);
 }
 

@@ -111,14 +111,16 @@ struct LinesKey {
     }
 };
 std::mutex g_lines_mutex;
-std::map<LinesKey, double*> g_lines;
+// (never destroyed: the buffers stay, as they always have, until the process ends -- freeing them from a static destructor would
+// call into a runtime that may be gone)
+std::map<LinesKey, DeviceBuffer<double>>& g_lines = *new std::map<LinesKey, DeviceBuffer<double>>;
 
 int device_lines(const char* who, int device, int sd, int nn, const double* nodes, const double** out) {
     LinesKey key{device, sd, nn, std::vector<double>(nodes, nodes + (size_t)sd * nn)};
     std::lock_guard<std::mutex> lock(g_lines_mutex);
     auto it = g_lines.find(key);
     if (it != g_lines.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return FX_OK;
     }
     if (g_lines.size() >= CM_MAX_LINE_SETS) {
@@ -128,8 +130,7 @@ int device_lines(const char* who, int device, int sd, int nn, const double* node
         }
         for (auto& kv : g_lines) {
             FX_HIP_TRY(hipSetDevice(kv.first.device));
-            FX_HIP_TRY(hipFree(kv.second));
-            kv.second = nullptr;
+            FX_HIP_TRY(kv.second.reset());
         }
         g_lines.clear();
     }
@@ -157,17 +158,12 @@ int device_lines(const char* who, int device, int sd, int nn, const double* node
             D[j * nn + j] = -s;
         }
     }
-    double* d = nullptr;
+    DeviceBuffer<double> d;
     FX_HIP_TRY(hipSetDevice(device));
-    FX_HIP_TRY(hipMalloc(&d, buf.size() * 8));
-    hipError_t e = hipMemcpy(d, buf.data(), buf.size() * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        (void)hipGetLastError();
-        return fail(FX_EHIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    g_lines.emplace(std::move(key), d);
-    *out = d;
+    const hipError_t e = d.upload(buf.data(), buf.size());
+    if (e != hipSuccess) return fail(FX_EHIP, "%s: %s", who, hipGetErrorString(e));
+    *out = d.get();
+    g_lines.emplace(std::move(key), std::move(d));
     return FX_OK;
 }
 

@@ -11,14 +11,15 @@
 #include "../../include/fiat_amd_eval.h"
 #include "evaluate.hpp"
 #include "host_common.hpp"
+#include <memory>
 
 struct fx_eval_element {
     fx_ctx* ctx = nullptr;
     int sd = 0, n = 0, variant = 0, ndof = 0, vdim = 1, nexp = 0;
     double phi0 = 0.0;
     double A0[9] = {0}, b0[3] = {0};
-    double* d_Ap = nullptr;    // A'[ndof][vdim][nexp], columns in the order of the walk
-    double* d_coef = nullptr;  // [nexp][3]
+    DeviceBuffer<double> d_Ap;    // A'[ndof][vdim][nexp], columns in the order of the walk
+    DeviceBuffer<double> d_coef;  // [nexp][3]
 };
 
 namespace {
@@ -127,7 +128,7 @@ int fx_eval_element_create(fx_ctx* ctx, int sd, int degree, int variant, double 
         for (int i = 1; i <= sd; ++i) vol *= 2.0 / i;
         scale = std::sqrt(1.0 / vol);
     }
-    fx_eval_element* e = new fx_eval_element;
+    std::unique_ptr<fx_eval_element> e(new fx_eval_element);
     e->ctx = ctx;
     e->sd = sd;
     e->n = degree;
@@ -139,10 +140,7 @@ int fx_eval_element_create(fx_ctx* ctx, int sd, int degree, int variant, double 
     double A[9], b[3];
     sd == 1 ? cell_map<1>(v, A, b) : sd == 2 ? cell_map<2>(v, A, b) : cell_map<3>(v, A, b);
     for (int i = 0; i < sd * sd; ++i) {
-        if (!std::isfinite(A[i])) {
-            delete e;
-            return fail(FX_EINVAL, "%s: degenerate cell", who);
-        }
+        if (!std::isfinite(A[i])) return fail(FX_EINVAL, "%s: degenerate cell", who);
         e->A0[i] = A[i];
     }
     for (int i = 0; i < sd; ++i) e->b0[i] = b[i];
@@ -152,23 +150,17 @@ int fx_eval_element_create(fx_ctx* ctx, int sd, int degree, int variant, double 
     int device = 0, num_cu = 0, lds_per_cu = 0;
     fx::ctx_facts(ctx, &device, &num_cu, &lds_per_cu);
     hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = hipMalloc(&e->d_Ap, F.size() * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc(&e->d_coef, t.coef.size() * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpy(e->d_Ap, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(e->d_coef, t.coef.data(), t.coef.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = e->d_Ap.upload(F.data(), F.size());
+    if (he == hipSuccess) he = e->d_coef.upload(t.coef.data(), t.coef.size());
     if (he != hipSuccess) {
-        (void)hipGetLastError();
-        fx_eval_element_destroy(e);
+        (void)hipGetLastError();  // (a failed hipSetDevice)
         return fail(FX_EHIP, "%s: %s", who, hipGetErrorString(he));
     }
-    *elem = e;
+    *elem = e.release();
     return FX_OK;
 }
 
 int fx_eval_element_destroy(fx_eval_element* e) {
-    if (!e) return FX_OK;
-    if (e->d_Ap) (void)hipFree(e->d_Ap);
-    if (e->d_coef) (void)hipFree(e->d_coef);
     delete e;
     return FX_OK;
 }
@@ -228,12 +220,13 @@ int fx_eval_batch(fx_ctx* ctx, const fx_eval_element* e, int mapping, int order,
     hipStream_t s = (hipStream_t)stream;
     FX_HIP_TRY(hipSetDevice(device));
     const bool vec = e->vdim > 1;
+    const double *Ap = e->d_Ap.get(), *coef = e->d_coef.get();
     hipError_t he;
-    if (e->sd == 1) he = launch_order<1, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
-    else if (e->sd == 2) he = vec ? launch_order<2, 2>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out)
-                                  : launch_order<2, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
-    else he = vec ? launch_order<3, 3>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out)
-                  : launch_order<3, 1>(order, grid, p.lds, s, a, pts, verts, dofs, e->d_Ap, e->d_coef, out);
+    if (e->sd == 1) he = launch_order<1, 1>(order, grid, p.lds, s, a, pts, verts, dofs, Ap, coef, out);
+    else if (e->sd == 2) he = vec ? launch_order<2, 2>(order, grid, p.lds, s, a, pts, verts, dofs, Ap, coef, out)
+                                  : launch_order<2, 1>(order, grid, p.lds, s, a, pts, verts, dofs, Ap, coef, out);
+    else he = vec ? launch_order<3, 3>(order, grid, p.lds, s, a, pts, verts, dofs, Ap, coef, out)
+                  : launch_order<3, 1>(order, grid, p.lds, s, a, pts, verts, dofs, Ap, coef, out);
     FX_HIP_TRY(he);
     return FX_OK;
 }

@@ -1,5 +1,5 @@
-// Host scaffold of the wave-per-item kernel families (bernstein, hdivcurl, serendipity, sforms, dpc, trace, hierarchical,
-// evaluate .hip): the error slot, the item plan, the grid and the launch.  Everything has internal linkage: each family is
+// Host scaffold of the main library (api.hip) and the wave-per-item kernel families (bernstein, hdivcurl, serendipity, sforms,
+// dpc, trace, hierarchical, evaluate, cellmap .hip): the error slot, the device buffers, the item plan, the grid and the launch.  Everything has internal linkage: each family is
 // its own translation unit, most of them their own library, and none exports these names.  What a family keeps for itself:
 // its validation and message texts, its Args, its kernel and its item loop.
 #pragma once
@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "../../include/fiat_amd.h"
+#include "device_buffer.hpp"
 
 namespace fx {
 int set_error(int code, const char* msg);  // api.hip (libfiat_amd.so): one error slot, shared contexts
@@ -36,6 +37,22 @@ int fail(int code, const char* fmt, ...) {
             return fail(FX_EHIP, "%s: %s", #expr, hipGetErrorString(e_));         \
         }                                                                         \
     } while (0)
+
+// The one place where device memory is allocated and freed (device_buffer.hpp).
+struct HipMemory {
+    using error_t = hipError_t;
+    using stream_t = hipStream_t;
+    static constexpr hipError_t ok = hipSuccess;
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t free(void* p) { return hipFree(p); }
+    static hipError_t copy_in(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+    static hipError_t zero(void* dst, size_t bytes) { return hipMemset(dst, 0, bytes); }
+    static hipError_t alloc_async(void** p, size_t bytes, hipStream_t s) { return hipMallocAsync(p, bytes, s); }
+    static hipError_t free_async(void* p, hipStream_t s) { return hipFreeAsync(p, s); }
+    static void clear_error() { (void)hipGetLastError(); }
+};
+template <class T> using DeviceBuffer = fx::DeviceBuffer<T, HipMemory>;
+template <class T> using StreamScratch = fx::StreamScratch<T, HipMemory>;
 
 // How the requests of a launch are grouped into items, one wave each.  An item is P whole requests, as many as 64 lanes
 // hold at one point per lane (one request in chunks of 64 points beyond).  Where requests of `reqsize` doubles fit

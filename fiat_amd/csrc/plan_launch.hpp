@@ -661,7 +661,7 @@ int choose_stacked(const Request& rq, const FixedChoice& fixed, const SmallChoic
             if (rc != FX_OK) return rc;
             if (e->stack_state[order] != 1) continue;
             const bool dofmajor = inmix || wg.mix;
-            const double* afrag = pio ? e->d_astack_dmp[order] : dofmajor ? e->d_astack_dm[order] : e->d_astack[order];
+            const double* afrag = pio ? e->d_astack_dmp[order].get() : dofmajor ? e->d_astack_dm[order].get() : e->d_astack[order].get();
             if (!afrag) continue;
             if (dofmajor && !invert_small(e->sd, e->A0, out.A0inv)) continue;
             const bool mixr = pio || mix_odd || k.mixr;  // of the twin run_stacked will take
@@ -718,8 +718,8 @@ void fill_generic(Launch& L, const Request& rq, const GenericShape& g, const dou
     const fx_element* e = rq.e;
     fxk::TabArgs& a = L.args;
     fill_header(a, rq, pts, verts, out);
-    a.afrag = e->d_afrag;
-    a.steps = e->d_steps;
+    a.afrag = e->d_afrag.get();
+    a.steps = e->d_steps.get();
     a.rows = rq.rows;
     a.nexp = e->nexp;
     a.nsteps = (int)e->prog.steps.size();
@@ -743,10 +743,10 @@ void fill_coop(Launch& L, const Request& rq, const CoopChoice& c, const double* 
     const fx_element* e = rq.e;
     fxk::CoopArgs& ca = L.cargs;
     fill_header(ca, rq, pts, verts, out);
-    ca.afrag = e->d_afrag_coop;
-    ca.eint = e->d_coop_eint;
-    ca.edbl = e->d_coop_edbl;
-    ca.kstart = e->d_coop_kstart;
+    ca.afrag = e->d_afrag_coop.get();
+    ca.eint = e->d_coop_eint.get();
+    ca.edbl = e->d_coop_edbl.get();
+    ca.kstart = e->d_coop_kstart.get();
     ca.rows = rq.rows;
     ca.KS = e->coop_KS;
     ca.NT = c.nt_need;
@@ -793,9 +793,9 @@ void fill_fixed(Launch& L, const Request& rq, const FixedChoice& f, const double
     }
     L.fkind = f.fkind;
     L.ncu = rq.num_cu;
-    L.trash = rq.ctx->d_trash;
+    L.trash = rq.ctx->d_trash.get();
     L.ctx = rq.ctx;   // (the paired kernel draws its work counter at the launch, when the stream is known: work_counter)
-    fa.afrag = f.fkind >= 1 ? e->d_afrag_stream : e->d_afrag_split;
+    fa.afrag = f.fkind >= 1 ? e->d_afrag_stream.get() : e->d_afrag_split.get();
     fa.debug = (rq.debug & 0xffff) | (f.fuses ? (rq.mapping << 16) : 0);
     fa.lds_doubles = f.lds_doubles;
     L.flds_bytes = f.lds_bytes;
@@ -810,7 +810,7 @@ void fill_small(Launch& L, const Request& rq, const SmallChoice& s, const double
         sa.piola = rq.mapping;
         for (int q = 0; q < 9; ++q) sa.G[q] = 0.5 * e->A0[q];
     }
-    sa.cmat = e->d_cmat;
+    sa.cmat = e->d_cmat.get();
     copy_abc(e->prog, sa.coef);
     sa.nitems = (rq.nreq + s.P - 1) / s.P;
     sa.rows = rq.rows;
@@ -852,7 +852,7 @@ void fill_stacked(Launch& L, const Request& rq, const StackedChoice& c, const do
     }
     L.kgrid = c.grid;
     L.ncu = rq.num_cu;
-    L.trash = rq.ctx->d_trash;
+    L.trash = rq.ctx->d_trash.get();
     L.ctx = rq.ctx;
     L.kmix_order = rq.order;
     L.kodd = c.kodd;

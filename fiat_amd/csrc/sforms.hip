@@ -10,11 +10,12 @@
 #include "../../include/fiat_amd_sforms.h"
 #include "sforms.hpp"
 #include "host_common.hpp"
+#include <memory>
 
 struct fx_sforms_element {
     int device, sd, degree, nrows;
-    double* coef;  // device [nrows * sd]
-    int* codes;    // device [nrows * sd]
+    DeviceBuffer<double> coef;  // [nrows * sd]
+    DeviceBuffer<int> codes;    // [nrows * sd]
 };
 
 namespace {
@@ -90,26 +91,15 @@ int fx_sforms_element_create(fx_ctx* ctx, int sd, int degree, int nrows, const d
     int device = 0, num_cu = 0, lds_per_cu = 0;
     fx::ctx_facts(ctx, &device, &num_cu, &lds_per_cu);
     FX_HIP_TRY(hipSetDevice(device));
-    fx_sforms_element* el = new fx_sforms_element{device, sd, degree, nrows, nullptr, nullptr};
-    hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&el->coef), npad * sizeof(double));
-    hipError_t e2 = e1 == hipSuccess ? hipMalloc(reinterpret_cast<void**>(&el->codes), npad * sizeof(int)) : e1;
-    if (e2 == hipSuccess) e2 = hipMemcpy(el->coef, padded.data(), npad * sizeof(double), hipMemcpyHostToDevice);
-    if (e2 == hipSuccess) e2 = hipMemcpy(el->codes, packed.data(), npad * sizeof(int), hipMemcpyHostToDevice);
-    if (e2 != hipSuccess) {
-        (void)hipGetLastError();
-        if (el->coef) (void)hipFree(el->coef);
-        if (el->codes) (void)hipFree(el->codes);
-        delete el;
-        return fail(e2 == hipErrorOutOfMemory ? FX_ENOMEM : FX_EHIP, "%s: %s", who, hipGetErrorString(e2));
-    }
-    *out = el;
+    std::unique_ptr<fx_sforms_element> el(new fx_sforms_element{device, sd, degree, nrows, {}, {}});
+    hipError_t e = el->coef.upload(padded.data(), npad);
+    if (e == hipSuccess) e = el->codes.upload(packed.data(), npad);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FX_ENOMEM : FX_EHIP, "%s: %s", who, hipGetErrorString(e));
+    *out = el.release();
     return FX_OK;
 }
 
 int fx_sforms_element_destroy(fx_sforms_element* el) {
-    if (!el) return FX_OK;
-    (void)hipFree(el->coef);
-    (void)hipFree(el->codes);
     delete el;
     return FX_OK;
 }
@@ -144,8 +134,8 @@ int fx_sforms_tabulate_batch(fx_ctx* ctx, const fx_sforms_element* el, const dou
     memset(&a, 0, sizeof a);
     a.pts = pts;
     a.out = out;
-    a.coef = el->coef;
-    a.codes = el->codes;
+    a.coef = el->coef.get();
+    a.codes = el->codes.get();
     for (int d = 0; d < 3; ++d) {
         a.v0[d] = d < el->sd ? lo[d] : 0.0;
         a.v1[d] = d < el->sd ? hi[d] : 1.0;

@@ -384,6 +384,32 @@ def test_set_coeffs_rebuilds_the_internal_element():
             H.assert_close(cells[r], H.chain_rule_tables(want, sd, ORDER, verts[r]), sd, ORDER, ("cells", r))
 
 
+def test_set_coeffs_with_another_ndof_drops_every_cache(kernel_policy):
+    """A P2 triangle, 2 requests of 3 points on its own cell under policy stacked_small: orders 0 and 2 build the stacked matrices
+    of the element, order 3 its internal element.  fx_element_set_coeffs with 4 rows in place of 6 replaces the coefficient
+    buffers and drops all of those; the same orders afterwards are the new matrix times the tables of a fresh
+    identity-coefficient element of the same expansion set."""
+    import fiat_amd as fa
+    sd, n, orders = 2, 2, (0, 2, 3)
+    kernel_policy("stacked_small")
+    ps = fa.Lagrange(fa.ufc_simplex(sd), n).get_nodal_basis()
+    es, C6 = ps.get_expansion_set(), np.asarray(ps.get_coeffs(), dtype=float)
+    ref_pts, _, _ = requests(sd, 2, 3, 11)
+    raw = es.device_polyset(n)                                               # identity coefficients: the expansion set itself
+    phi = {k: raw.tabulate_batch(k, ref_pts).cpu().numpy() for k in orders}  # (nreq, ntab, nexp, npts)
+    dev = es.device_polyset(n, coeffs=C6)
+    C4 = np.random.default_rng(89).standard_normal((4, C6.shape[1]))
+    for C in (C6, C4):
+        if C is not C6:
+            dev.set_coeffs(C)
+        for k in orders:
+            got = dev.tabulate_batch(k, ref_pts).cpu().numpy()
+            assert got.shape == (2, H.ntables(sd, k), C.shape[0], 3)
+            for r in range(2):
+                want = np.einsum("ij,tjp->tip", C, phi[k][r])
+                show(f"set_coeffs {C.shape} order {k}, request {r}", H.assert_close(got[r], want, sd, k, (C.shape, k, r)))
+
+
 @pytest.mark.parametrize("name", ["rt8tri", "on10int"])
 def test_order_9_is_refused(golden, name):
     g = golden("high_order")
